@@ -13,6 +13,14 @@ token (N tokens whole-job per step).  Warmup = prefill + W untimed
 rotations.  The timed region is exactly K rotations bracketed by
 barrier + torch.cuda.synchronize() on both sides; the reported time is the
 MAX over ranks.  Rank 0 prints ONE JSON line.
+
+A plain run does only that: set up, warm up, time the K rotations, print.
+--dump-outputs DIR additionally writes the last timed step's results
+(tokens, and the HIP engine's last logits) as DIR/<name>.npy so two builds
+can be compared output for output; weights, prompts and the sampler are
+seeded, so the same arguments give the same arrays.  --full is the switch
+for anything measured or checked beyond the headline figure; nothing of
+that kind lives in this file today, so it changes nothing yet.
 """
 
 import argparse
@@ -46,7 +54,46 @@ def parse_args():
                     help="KV-cache dtype (fp8 = e4m3 per-row-scaled cache; "
                          "NOT the headline config — reported in dtype)")
     ap.add_argument("--no-graphs", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the timed path "
+                         "returned in its last step as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements and checks beyond the "
+                         "headline figure (there are none today: a plain "
+                         "run already does only setup, warmup and the "
+                         "timed steps)")
     return ap.parse_args()
+
+
+def dump_outputs(out_dir, toks, runner, geng, vocab_size):
+    """Write the last timed step's results as float32 .npy files.
+
+    tokens      [n_samples]  the per-sample tokens the decode phase hands
+                             back to its caller (token ids are < 2**24, so
+                             float32 holds them exactly)
+    last_logits [lanes, V]   HIP engine only: the logits the last step
+                             sampled from, one row per lane workspace (the
+                             drawn token can flip on a rounding-level logit
+                             change; the logits themselves compare smoothly)
+    Inputs are seeded (weights, prompts, sampler), so the same arguments
+    give the same arrays from run to run."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    if geng is not None:
+        tokens = geng.token_table
+    else:
+        tokens = torch.cat([t.view(1) for t in toks])
+    np.save(os.path.join(out_dir, "tokens.npy"),
+            tokens.detach().to("cpu", torch.float32).numpy())
+    eng = getattr(runner, "engine", None) if geng is None else None
+    if runner.backend == "hip" and eng is not None:
+        lanes = getattr(eng, "_lane_bufs", None) or [{"logits": eng.logits}]
+        rows = [lb["logits"] for lb in lanes if lb.get("logits") is not None]
+        if rows:
+            logits = torch.stack(rows)[:, :vocab_size]
+            np.save(os.path.join(out_dir, "last_logits.npy"),
+                    logits.detach().to("cpu", torch.float32).numpy())
 
 
 def log(msg):
@@ -282,6 +329,9 @@ def main():
                 "backend": runner.backend,
             },
         }
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, toks, runner, geng,
+                         cfg.vocab_size)
         print(json.dumps(out), flush=True)
 
     if world > 1:

@@ -79,6 +79,31 @@ def test_bench_cpu_mode(tmp_path):
     assert '"n_gpus": 2' in r.stdout
 
 
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """--dump-outputs writes the last step's tokens as float32 .npy; the
+    same arguments give the same arrays (seeded inputs), --steps sets the
+    number of timed steps, and --full still ends with the result line."""
+    import json
+
+    import numpy as np
+
+    dumps = []
+    for d, extra in (("a", []), ("b", ["--full"])):
+        r = run(["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1",
+                 "--model", "nano-test", "--prompt-len", "8", "--seq-len",
+                 "64", "--samples", "2", "--dump-outputs",
+                 str(tmp_path / d)] + extra)
+        assert r.returncode == 0, r.stderr[-2000:]
+        res = json.loads(r.stdout.strip().splitlines()[-1])
+        assert res["steps"] == 3 and res["ms_per_step"] > 0
+        assert res["value"] == pytest.approx(
+            2 * 1000.0 / res["ms_per_step"], rel=1e-2)
+        t = np.load(tmp_path / d / "tokens.npy")
+        assert t.dtype == np.float32 and t.shape == (2,)
+        dumps.append(t)
+    assert np.array_equal(dumps[0], dumps[1])
+
+
 @pytest.mark.parametrize("world", [4, 8])
 def test_bench_cpu_mode_wide(world):
     """The exact flow the driver runs on the 8-GPU node (torchrun, one

@@ -12,7 +12,8 @@ into the modules instead — gptserver.py:975-978).
 Supported natively: RMSNorm/LayerNorm, rope/learned positions, GQA
 attention (head_size multiple of 32, head_size*q_per_kv >= 64), LLaMA
 (SwiGLU) / Gemma / GPT-NeoX MLPs, sequential and parallel residual.
-MoE decodes natively (device-side routing); fp8+MoE is refused.
+MoE decodes natively (device-side routing); fp8+MoE and int4+MoE are
+refused.
 """
 
 from __future__ import annotations
@@ -54,6 +55,75 @@ def quantize_fp8_rowwise(w: torch.Tensor):
     s = (wf.abs().amax(dim=1).clamp(min=1e-12) / 448.0).float()
     q = (wf / s[:, None]).to(torch.float8_e4m3fn)
     return q.contiguous(), s.contiguous()
+
+
+INT4_GROUP = 128
+
+
+def quantize_int4_groupwise(w: torch.Tensor):
+    """bf16 [M,K] -> (packed uint8 [M,Kp/2], bf16 qparams [M,Kp/128,2]).
+
+    Asymmetric 4-bit quantization over groups of 128 consecutive k:
+    scale = (max-min)/15, zero = min, both stored as bf16 (qparams[...,0]
+    and [...,1]); nib = round((w-zero)/scale) in 0..15 against the
+    bf16-rounded parameters, so w ~= nib*scale + zero exactly as the
+    kernel computes it.  K is padded to Kp = ceil(K/128)*128 with zero
+    nibbles (the padded positions take no part in a group's min/max).
+
+    Nibble order (what gemv_int4_kernel unpacks): each 8 consecutive k
+    form one little-endian 32-bit word whose low half holds the even k and
+    whose high half the odd k: n0 | n2<<4 | n4<<8 | n6<<12 | n1<<16 |
+    n3<<20 | n5<<24 | n7<<28, i.e. bytes (n0|n2<<4, n4|n6<<4, n1|n3<<4,
+    n5|n7<<4)."""
+    assert w.dim() == 2
+    M, K = w.shape
+    G = -(-K // INT4_GROUP)
+    Kp = G * INT4_GROUP
+    wf = w.detach().float()
+    pad = Kp - K
+    if pad:
+        inf = float("inf")
+        lo = torch.nn.functional.pad(wf, (0, pad), value=inf)
+        hi = torch.nn.functional.pad(wf, (0, pad), value=-inf)
+        wf = torch.nn.functional.pad(wf, (0, pad))
+    else:
+        lo = hi = wf
+    mn = lo.view(M, G, INT4_GROUP).amin(dim=2)
+    mx = hi.view(M, G, INT4_GROUP).amax(dim=2)
+    del lo, hi
+    scale = ((mx - mn) / 15.0).to(torch.bfloat16)
+    # constant group: any nonzero scale dequantizes nib 0 to the constant
+    scale = torch.where(scale == 0, torch.ones_like(scale), scale)
+    zero = mn.to(torch.bfloat16)
+    nib = ((wf.view(M, G, INT4_GROUP) - zero.float()[..., None])
+           / scale.float()[..., None]).round_().clamp_(0, 15)
+    nib = nib.view(M, Kp).to(torch.uint8)
+    if pad:
+        nib[:, K:] = 0
+    n = nib.view(M, Kp // 8, 8)
+    packed = torch.stack(
+        [n[..., 0] | (n[..., 2] << 4), n[..., 4] | (n[..., 6] << 4),
+         n[..., 1] | (n[..., 3] << 4), n[..., 5] | (n[..., 7] << 4)],
+        dim=2).view(M, Kp // 2)
+    qparams = torch.stack([scale, zero], dim=2)
+    return packed.contiguous(), qparams.contiguous()
+
+
+def dequantize_int4(packed: torch.Tensor, qparams: torch.Tensor,
+                    K: int) -> torch.Tensor:
+    """Exact inverse mapping of quantize_int4_groupwise: fp32 [M,K] of
+    nib*scale + zero from the stored bf16 parameters (pure torch)."""
+    M = packed.size(0)
+    Kp = packed.size(1) * 2
+    b = packed.view(M, Kp // 8, 4)
+    lo, hi = b & 0xF, b >> 4
+    nib = torch.stack(
+        [lo[..., 0], lo[..., 2], hi[..., 0], hi[..., 2],
+         lo[..., 1], lo[..., 3], hi[..., 1], hi[..., 3]],
+        dim=2).view(M, Kp // INT4_GROUP, INT4_GROUP).float()
+    q = qparams.float()
+    w = nib * q[..., 0:1] + q[..., 1:2]
+    return w.view(M, Kp)[:, :K].contiguous()
 
 
 class _BlockWeights:
@@ -114,6 +184,21 @@ class _BlockWeights:
         else:
             self.fc_w8, self.fc_s = quantize_fp8_rowwise(self.fc_w)
 
+    def quantize_int4(self, config) -> None:
+        """Attach packed int4 copies + per-group (scale, zero) for the
+        decode GEMVs."""
+        if config.mlp_class_name == "LLaMAMoE":
+            raise ValueError("int4 weights are not supported for MoE stages")
+        names = ["attn_w", "proj_w", "mlp_proj_w"]
+        if config.mlp_class_name in ("LLaMAMLP", "GemmaMLP"):
+            names += ["fc1_w", "fc2_w"]
+        else:
+            names += ["fc_w"]
+        for n in names:
+            packed, qparams = quantize_int4_groupwise(getattr(self, n))
+            setattr(self, n + "4", packed)
+            setattr(self, n[:-2] + "_q", qparams)
+
 
 class DecodeEngine:
     """Drives the HIP kernels for a stage (Starter or Secondary module)."""
@@ -166,9 +251,18 @@ class DecodeEngine:
         self.blocks = [_BlockWeights(b, cfg) for b in stage.transformer.h]
         self.fp8 = (self.weight_dtype == "fp8"
                     and self.device.type == "cuda")
+        # int4 (128-group, bf16 scale/zero): the smallest decode weight
+        # stream.  Like fp8, only the decode GEMVs read the quantized
+        # copies; prefill keeps the bf16 weights (so this saves decode
+        # bandwidth, not memory).
+        self.int4 = (self.weight_dtype == "int4"
+                     and self.device.type == "cuda")
         if self.fp8:
             for w in self.blocks:
                 w.quantize_fp8(cfg)
+        if self.int4:
+            for w in self.blocks:
+                w.quantize_int4(cfg)
         if self.is_starter:
             self.wte = stage.transformer.wte.weight.detach().contiguous()
             self.lnf_w = stage.transformer.ln_f.weight.detach().contiguous()
@@ -178,6 +272,9 @@ class DecodeEngine:
             self.head_w = stage.lm_head.weight.detach().contiguous()
             if self.fp8:
                 self.head_w8, self.head_s = quantize_fp8_rowwise(self.head_w)
+            if self.int4:
+                self.head_w4, self.head_q = quantize_int4_groupwise(
+                    self.head_w)
             self.head_b = stage.lm_head.bias
             if self.head_b is not None:
                 self.head_b = self.head_b.detach().contiguous()
@@ -260,6 +357,7 @@ class DecodeEngine:
         K_attn = cfg.n_head * cfg.head_size
         self._fuse_attn_proj = (
             not self.fp8
+            and not self.int4
             and not self.kv8
             and not cfg.parallel_residual
             and stage.max_seq_length <= 4096
@@ -361,6 +459,27 @@ class DecodeEngine:
         )
         return self.sample_out
 
+    def _gemv(self, out, w, name, x, bias, res, epilogue, norm_w, norm_b,
+              norm_kind, rows) -> None:
+        """out = epilogue(W @ norm?(x)) for the weight `name` held by `w`
+        (a _BlockWeights, or the engine itself for the lm_head), in the
+        engine's weight mode: <name>_w bf16, <name>_w8/<name>_s fp8,
+        <name>_w4/<name>_q int4."""
+        eps = self.config.norm_eps
+        if self.int4:
+            self.ops.gemv_int4(out, getattr(w, name + "_w4"),
+                               getattr(w, name + "_q"), x, bias, res,
+                               epilogue, norm_w, norm_b, norm_kind, eps,
+                               rows)
+        elif self.fp8:
+            self.ops.gemv_fp8(out, getattr(w, name + "_w8"),
+                              getattr(w, name + "_s"), x, bias, res,
+                              epilogue, norm_w, norm_b, norm_kind, eps,
+                              rows)
+        else:
+            self.ops.gemv(out, getattr(w, name + "_w"), x, bias, res,
+                          epilogue, norm_w, norm_b, norm_kind, eps, rows)
+
     def _run_blocks(self) -> None:
         """x -> x through all local blocks (decode, one token).
 
@@ -375,13 +494,8 @@ class DecodeEngine:
         for li, w in enumerate(self.blocks):
             # qkv = Wqkv @ norm1(x); rope + kv-append are fused inside the
             # attention kernel (qkv stays raw)
-            if self.fp8:
-                ops.gemv_fp8(self.qkv, w.attn_w8, w.attn_s, self.x,
-                             w.attn_b, None, 0, w.norm1_w, w.norm1_b, nk,
-                             eps, self._r_qkv)
-            else:
-                ops.gemv(self.qkv, w.attn_w, self.x, w.attn_b, None, 0,
-                         w.norm1_w, w.norm1_b, nk, eps, self._r_qkv)
+            self._gemv(self.qkv, w, "attn", self.x, w.attn_b, None, 0,
+                       w.norm1_w, w.norm1_b, nk, self._r_qkv)
             if self._fuse_attn_proj:
                 # attention + proj + residual add in ONE launch; the proj
                 # rows stream into LDS while the attention blocks run
@@ -400,26 +514,16 @@ class DecodeEngine:
             )
             if cfg.parallel_residual:
                 # x = x + proj(y) + mlp(norm2(x) or norm1(x))
-                if self.fp8:
-                    ops.gemv_fp8(self.a, w.proj_w8, w.proj_s, self.y,
-                                 w.proj_b, None, 0, None, None, 0, eps,
-                                 self._r_proj)
-                else:
-                    ops.gemv(self.a, w.proj_w, self.y, w.proj_b, None, 0,
-                             None, None, 0, eps, self._r_proj)
+                self._gemv(self.a, w, "proj", self.y, w.proj_b, None, 0,
+                           None, None, 0, self._r_proj)
                 nw = w.norm1_w if cfg.shared_attention_norm else w.norm2_w
                 nb = w.norm1_b if cfg.shared_attention_norm else w.norm2_b
                 self._mlp(self.x, w, self.a, nw, nb)
                 ops.add(self.x, self.x, self.m_out)
             else:
                 # a = x + proj(y); x = a + mlp(norm2(a))
-                if self.fp8:
-                    ops.gemv_fp8(self.a, w.proj_w8, w.proj_s, self.y,
-                                 w.proj_b, self.x, 1, None, None, 0, eps,
-                                 self._r_proj)
-                else:
-                    ops.gemv(self.a, w.proj_w, self.y, w.proj_b, self.x, 1,
-                             None, None, 0, eps, self._r_proj)
+                self._gemv(self.a, w, "proj", self.y, w.proj_b, self.x, 1,
+                           None, None, 0, self._r_proj)
                 self._mlp(self.a, w, self.a, w.norm2_w, w.norm2_b)
                 # _mlp wrote x = res + down(act) directly
         # (sequential path leaves the stream in self.x)
@@ -462,27 +566,23 @@ class DecodeEngine:
             return
         if cfg.mlp_class_name in ("LLaMAMLP", "GemmaMLP"):
             gelu_gate = cfg.mlp_class_name == "GemmaMLP"
-            if self.fp8:
+            if self.int4:
+                self.ops.gemv_swiglu_int4(self.act, w.fc1_w4, w.fc1_q,
+                                          w.fc2_w4, w.fc2_q, inp, gelu_gate,
+                                          norm_w, norm_b, nk, eps)
+            elif self.fp8:
                 self.ops.gemv_swiglu_fp8(self.act, w.fc1_w8, w.fc1_s,
                                          w.fc2_w8, w.fc2_s, inp, gelu_gate,
                                          norm_w, norm_b, nk, eps)
             else:
                 self.ops.gemv_swiglu(self.act, w.fc1_w, w.fc2_w, inp,
                                      gelu_gate, norm_w, norm_b, nk, eps)
-        elif self.fp8:
-            self.ops.gemv_fp8(self.act, w.fc_w8, w.fc_s, inp, w.fc_b, None,
-                              2, norm_w, norm_b, nk, eps, 0)
         else:
-            self.ops.gemv(self.act, w.fc_w, inp, w.fc_b, None, 2,
-                          norm_w, norm_b, nk, eps)  # gelu
+            self._gemv(self.act, w, "fc", inp, w.fc_b, None, 2, norm_w,
+                       norm_b, nk, 0)  # gelu
         out = self.m_out if cfg.parallel_residual else self.x
-        if self.fp8:
-            self.ops.gemv_fp8(out, w.mlp_proj_w8, w.mlp_proj_s, self.act,
-                              w.mlp_proj_b, res, 1, None, None, 0, eps,
-                              self._r_down)
-        else:
-            self.ops.gemv(out, w.mlp_proj_w, self.act, w.mlp_proj_b, res, 1,
-                          None, None, 0, eps, self._r_down)
+        self._gemv(out, w, "mlp_proj", self.act, w.mlp_proj_b, res, 1,
+                   None, None, 0, self._r_down)
 
     def _embed(self) -> None:
         cfg = self.config
@@ -494,15 +594,8 @@ class DecodeEngine:
 
     def _tail_seq(self) -> None:
         # logits = lm_head @ ln_f(x): one fused kernel
-        if self.fp8:
-            self.ops.gemv_fp8(self.logits, self.head_w8, self.head_s,
-                              self.x, self.head_b, None, 0, self.lnf_w,
-                              self.lnf_b, self._nk, self.config.norm_eps,
-                              self._r_head)
-        else:
-            self.ops.gemv(self.logits, self.head_w, self.x, self.head_b,
-                          None, 0, self.lnf_w, self.lnf_b, self._nk,
-                          self.config.norm_eps, self._r_head)
+        self._gemv(self.logits, self, "head", self.x, self.head_b, None, 0,
+                   self.lnf_w, self.lnf_b, self._nk, self._r_head)
 
     # ---------------------------------------------------------------------
     # public decode API

@@ -90,6 +90,12 @@ class GroupDecodeEngine:
 
             warnings.warn("grouped decode ignores MDI_WEIGHT_DTYPE=fp8 "
                           "(bf16 is faster for batched GEMMs; see ROADMAP)")
+        # int4 weights exist only as B=1 decode GEMVs (DecodeEngine)
+        if os.environ.get("MDI_WEIGHT_DTYPE", "bf16") == "int4":
+            import warnings
+
+            warnings.warn("grouped decode ignores MDI_WEIGHT_DTYPE=int4 "
+                          "(int4 weights serve single-sample decode only)")
         self.fp8 = False
         self.config = cfg
         self.stage = stage

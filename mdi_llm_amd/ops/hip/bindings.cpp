@@ -171,6 +171,96 @@ void gemv_swiglu_fp8(torch::Tensor out, torch::Tensor Wg,
                          (int)norm_kind, cur_stream());
 }
 
+// packed int4 weights [M, Kp/2] (uint8) + bf16 (scale, zero) [M, Kp/128, 2]
+inline void check_int4(const torch::Tensor& W, const torch::Tensor& qparams,
+                       int M, int K, const char* name) {
+  const int64_t Kp = ((int64_t)K + 127) / 128 * 128;
+  TORCH_CHECK(W.is_cuda() && W.scalar_type() == torch::kUInt8 &&
+                  W.is_contiguous(),
+              name, " must be contiguous uint8 on GPU");
+  TORCH_CHECK(W.numel() == (int64_t)M * Kp / 2, name, " shape mismatch");
+  check_bf16(qparams, "qparams");
+  TORCH_CHECK(qparams.numel() == (int64_t)M * (Kp / 128) * 2,
+              "qparams shape mismatch");
+  TORCH_CHECK(Kp * 2 + Kp / 128 * 4 <= 64 * 1024,
+              "K too large for the staged int4 GEMV");
+}
+
+void gemv_int4(torch::Tensor out, torch::Tensor W, torch::Tensor qparams,
+               torch::Tensor x, c10::optional<torch::Tensor> bias,
+               c10::optional<torch::Tensor> res, int64_t epilogue,
+               c10::optional<torch::Tensor> norm_w,
+               c10::optional<torch::Tensor> norm_b, int64_t norm_kind,
+               double eps, int64_t rows) {
+  check_bf16(out, "out");
+  check_bf16(x, "x");
+  const int K = (int)x.numel();
+  const int M = (int)out.numel();
+  TORCH_CHECK(M > 0 && K > 0, "empty GEMV");
+  TORCH_CHECK(K % 8 == 0, "K must be a multiple of 8");
+  check_int4(W, qparams, M, K, "W");
+  const void* bp = nullptr;
+  const void* rp = nullptr;
+  const void* nwp = nullptr;
+  const void* nbp = nullptr;
+  if (bias.has_value()) {
+    check_bf16(*bias, "bias");
+    TORCH_CHECK(bias->numel() == M, "bias size");
+    bp = bias->data_ptr();
+  }
+  if (res.has_value()) {
+    check_bf16(*res, "res");
+    TORCH_CHECK(res->numel() == M, "res size");
+    rp = res->data_ptr();
+  }
+  if (norm_kind != 0) {
+    TORCH_CHECK(norm_w.has_value(), "norm_w required with norm_kind");
+    check_bf16(*norm_w, "norm_w");
+    TORCH_CHECK(norm_w->numel() == K, "norm_w size");
+    nwp = norm_w->data_ptr();
+    if (norm_b.has_value()) {
+      check_bf16(*norm_b, "norm_b");
+      TORCH_CHECK(norm_b->numel() == K, "norm_b size");
+      nbp = norm_b->data_ptr();
+    }
+  }
+  launch_gemv_int4(out.data_ptr(), W.data_ptr(), qparams.data_ptr(),
+                   x.data_ptr(), bp, rp, nwp, nbp, (float)eps, M, K,
+                   (int)epilogue, (int)norm_kind, (int)rows, cur_stream());
+}
+
+void gemv_swiglu_int4(torch::Tensor out, torch::Tensor Wg, torch::Tensor gq,
+                      torch::Tensor Wu, torch::Tensor uq, torch::Tensor x,
+                      bool gelu_gate, c10::optional<torch::Tensor> norm_w,
+                      c10::optional<torch::Tensor> norm_b, int64_t norm_kind,
+                      double eps) {
+  check_bf16(out, "out");
+  check_bf16(x, "x");
+  const int K = (int)x.numel();
+  const int M = (int)out.numel();
+  TORCH_CHECK(M > 0 && K > 0, "empty GEMV");
+  TORCH_CHECK(K % 8 == 0, "K must be a multiple of 8");
+  check_int4(Wg, gq, M, K, "Wg");
+  check_int4(Wu, uq, M, K, "Wu");
+  const void* nwp = nullptr;
+  const void* nbp = nullptr;
+  if (norm_kind != 0) {
+    TORCH_CHECK(norm_w.has_value(), "norm_w required with norm_kind");
+    check_bf16(*norm_w, "norm_w");
+    TORCH_CHECK(norm_w->numel() == K, "norm_w size");
+    nwp = norm_w->data_ptr();
+    if (norm_b.has_value()) {
+      check_bf16(*norm_b, "norm_b");
+      TORCH_CHECK(norm_b->numel() == K, "norm_b size");
+      nbp = norm_b->data_ptr();
+    }
+  }
+  launch_gemv_swiglu_int4(out.data_ptr(), Wg.data_ptr(), gq.data_ptr(),
+                          Wu.data_ptr(), uq.data_ptr(), x.data_ptr(), nwp,
+                          nbp, (float)eps, M, K, gelu_gate ? 1 : 0,
+                          (int)norm_kind, cur_stream());
+}
+
 void gemv_swiglu(torch::Tensor out, torch::Tensor Wg, torch::Tensor Wu,
                  torch::Tensor x, bool gelu_gate,
                  c10::optional<torch::Tensor> norm_w,
@@ -590,6 +680,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fused SwiGLU pair GEMV with fp8 weights",
         py::arg("out"), py::arg("Wg"), py::arg("gscale"), py::arg("Wu"),
         py::arg("uscale"), py::arg("x"), py::arg("gelu_gate"),
+        py::arg("norm_w") = c10::nullopt, py::arg("norm_b") = c10::nullopt,
+        py::arg("norm_kind") = 0, py::arg("eps") = 1e-5);
+  m.def("gemv_int4", &gemv_int4,
+        "decode GEMV with int4 group-quantized weights (128-group bf16 "
+        "scale/zero)",
+        py::arg("out"), py::arg("W"), py::arg("qparams"), py::arg("x"),
+        py::arg("bias"), py::arg("res"), py::arg("epilogue"),
+        py::arg("norm_w") = c10::nullopt, py::arg("norm_b") = c10::nullopt,
+        py::arg("norm_kind") = 0, py::arg("eps") = 1e-5,
+        py::arg("rows") = 0);
+  m.def("gemv_swiglu_int4", &gemv_swiglu_int4,
+        "fused SwiGLU pair GEMV with int4 group-quantized weights",
+        py::arg("out"), py::arg("Wg"), py::arg("gq"), py::arg("Wu"),
+        py::arg("uq"), py::arg("x"), py::arg("gelu_gate"),
         py::arg("norm_w") = c10::nullopt, py::arg("norm_b") = c10::nullopt,
         py::arg("norm_kind") = 0, py::arg("eps") = 1e-5);
   m.def("gemv_swiglu", &gemv_swiglu, "fused SwiGLU pair GEMV (+pre-norm)",

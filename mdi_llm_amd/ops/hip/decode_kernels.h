@@ -38,6 +38,21 @@ void launch_gemv_swiglu_fp8(void* out, const void* Wg, const float* gscale,
                             int gelu_gate, int norm_kind,
                             hipStream_t stream);
 
+// int4 group-quantized variants: W is [M, Kp/2] packed nibbles with
+// Kp = ceil(K/128)*128, qparams bf16 [M, Kp/128, 2] = (scale, zero) per
+// 128-group (w = nib*scale + zero); K here is the unpadded length of x
+void launch_gemv_int4(void* out, const void* W, const void* qparams,
+                      const void* x, const void* bias, const void* res,
+                      const void* norm_w, const void* norm_b, float eps,
+                      int M, int K, int epilogue, int norm_kind, int rows,
+                      hipStream_t stream);
+
+void launch_gemv_swiglu_int4(void* out, const void* Wg, const void* gq,
+                             const void* Wu, const void* uq, const void* x,
+                             const void* norm_w, const void* norm_b,
+                             float eps, int M, int K, int gelu_gate,
+                             int norm_kind, hipStream_t stream);
+
 void launch_gemv_swiglu(void* out, const void* Wg, const void* Wu,
                         const void* x, const void* norm_w, const void* norm_b,
                         float eps, int M, int K, int gelu_gate, int norm_kind,

@@ -905,6 +905,237 @@ __global__ void gemv_swiglu_fp8_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------
+// INT4 group-quantized weight variants: 128 consecutive k share one bf16
+// (scale, zero) pair, w = nib * scale + zero.  Rows are zero-padded to
+// Kp = ceil(K/128)*128 (Kp/2 bytes, a multiple of 64), so one lane's 16 B
+// load holds 32 weights of ONE group and four adjacent lanes share a group.
+//
+// Nibble order inside a 32-bit word (8 consecutive k): the low half holds
+// the even k, the high half the odd k —
+//   word = n0 | n2<<4 | n4<<8 | n6<<12 | n1<<16 | n3<<20 | n5<<24 | n7<<28
+// so ((word >> 4j) & 0x000F000F) | 0x43004300 is the bf16 pair
+// (128 + n[2j], 128 + n[2j+1]) (0x4300 = 128.0, whose low mantissa bits
+// hold 0..15 exactly), lined up with the LDS word (x[2j], x[2j+1]) for the
+// packed bf16 dot product (v_dot2c_f32_bf16): shift + and_or + dot2 per
+// TWO weights.  With d = sum (128 + nib) * x over a lane's 32 weights,
+//   sum_group w*x = scale * sum_lanes d + (zero - 128*scale) * sum_group x
+// so the zero-point and the 128 bias cost one FMA per lane per load, fed
+// by the per-group sums of the staged x kept in LDS behind xs.
+// ---------------------------------------------------------------------------
+using bf16x2_t = __attribute__((ext_vector_type(2))) __bf16;
+
+// After stage_x: zero-fill xs[K..Kp) and write the fp32 sum of the staged
+// (normalized) x of each 128-group to gs[Kp/128].  16 threads per group.
+DEVINL void stage_group_sums(bf16* xs, float* gs, int K, int Kp) {
+  const int tid = threadIdx.x;
+  for (int i = K + tid * 8; i < Kp; i += blockDim.x * 8)
+    *reinterpret_cast<int4*>(xs + i) = make_int4(0, 0, 0, 0);
+  const int sub = tid & 15;
+  for (int g = tid >> 4; g < (Kp >> 7); g += blockDim.x >> 4) {
+    const int k = g * 128 + sub * 8;
+    float s = 0.f;
+    if (k < K) {  // K is a multiple of 8; the padded tail sums as zero
+      bf16x8 v = load8(xs + k);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) s += b2f(v.v[j]);
+    }
+#pragma unroll
+    for (int off = 8; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+    if (sub == 0) gs[g] = s;
+  }
+  __syncthreads();
+}
+
+// the lane's 32 staged x values as 16 (x[2j], x[2j+1]) words
+struct x32w {
+  i32x4_t v[4];
+};
+
+DEVINL x32w load_x32(const bf16* xs) {
+  x32w r;
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+    r.v[q] = *reinterpret_cast<const i32x4_t*>(xs + q * 8);
+  return r;
+}
+
+// one 16 B load (32 weights of one group) against the lane's x; qp is the
+// group's (scale | zero << 16) bf16 pair, gsum the group's sum of x
+DEVINL float dot32_int4(const i32x4_t wq, const x32w& x, unsigned qp,
+                        float gsum) {
+  float d0 = 0.f, d1 = 0.f;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const unsigned w = (unsigned)wq[q];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const unsigned p = ((w >> (4 * j)) & 0x000F000Fu) | 0x43004300u;
+      const bf16x2_t wp = __builtin_bit_cast(bf16x2_t, p);
+      const bf16x2_t xp = __builtin_bit_cast(bf16x2_t, (unsigned)x.v[q][j]);
+      if (j & 1)
+        d1 = __builtin_amdgcn_fdot2_f32_bf16(wp, xp, d1, false);
+      else
+        d0 = __builtin_amdgcn_fdot2_f32_bf16(wp, xp, d0, false);
+    }
+  }
+  const float scale = __uint_as_float(qp << 16);
+  const float zero = __uint_as_float(qp & 0xFFFF0000u);
+  // four lanes share the group: each carries a quarter of its x-sum term
+  return scale * (d0 + d1) + 0.25f * (zero - 128.f * scale) * gsum;
+}
+
+template <int EPI, int NORM, int ROWS>
+__global__ void gemv_int4_kernel(bf16* __restrict__ out,
+                                 const unsigned char* __restrict__ W,
+                                 const unsigned* __restrict__ qparams,
+                                 const bf16* __restrict__ x,
+                                 const bf16* __restrict__ bias,
+                                 const bf16* __restrict__ res,
+                                 const bf16* __restrict__ nw,
+                                 const bf16* __restrict__ nb, float eps,
+                                 int M, int K) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  __shared__ float red[8];
+  const int Kp = (K + 127) & ~127;
+  const int rowb = Kp >> 1;  // packed bytes per row
+  const int ng = Kp >> 7;    // groups per row
+  bf16* xs = reinterpret_cast<bf16*>(smem);
+  float* gs = reinterpret_cast<float*>(smem + (size_t)Kp * sizeof(bf16));
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int rows_per_grid = gridDim.x * (blockDim.x >> 6) * ROWS;
+  const int row0 = (blockIdx.x * (blockDim.x >> 6) + wave) * ROWS;
+
+  // prefetch across the staging barrier (32 nibbles = one dwordx4 per lane)
+  i32x4_t wpre[ROWS];
+  const bool pre_ok = lane * 16 < rowb;
+#pragma unroll
+  for (int r = 0; r < ROWS; ++r)
+    if (pre_ok)
+      wpre[r] = load16_nt_u8(W + (size_t)min(row0 + r, M - 1) * rowb +
+                             lane * 16);
+
+  const float nscale = stage_x<NORM>(xs, x, nw, nb, K, eps, red);
+  stage_group_sums(xs, gs, K, Kp);
+
+  for (int row = row0; row < M; row += rows_per_grid) {
+    const unsigned char* wrow[ROWS];
+    const unsigned* qrow[ROWS];
+    float acc[ROWS];
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) {
+      const size_t rw = (size_t)min(row + r, M - 1);
+      wrow[r] = W + rw * rowb;
+      qrow[r] = qparams + rw * ng;
+      acc[r] = 0.f;
+    }
+    int istart = lane * 16;
+    if (row == row0 && pre_ok) {
+      const x32w xv = load_x32(xs + istart * 2);
+      const int g = istart >> 6;
+      const float gsum = gs[g];
+#pragma unroll
+      for (int r = 0; r < ROWS; ++r)
+        acc[r] += dot32_int4(wpre[r], xv, qrow[r][g], gsum);
+      istart += 64 * 16;
+    }
+    for (int i = istart; i < rowb; i += 64 * 16) {
+      const x32w xv = load_x32(xs + i * 2);
+      const int g = i >> 6;
+      const float gsum = gs[g];
+#pragma unroll
+      for (int r = 0; r < ROWS; ++r) {
+        const i32x4_t wq = load16_nt_u8(wrow[r] + i);
+        acc[r] += dot32_int4(wq, xv, qrow[r][g], gsum);
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) acc[r] = wave_reduce_sum(acc[r]);
+    if (lane == 0) {
+#pragma unroll
+      for (int r = 0; r < ROWS; ++r) {
+        const int rw = row + r;
+        if (rw >= M) break;
+        float a = acc[r] * nscale;
+        if (bias != nullptr) a += b2f(bias[rw]);
+        if (EPI == 1 && res != nullptr) a += b2f(res[rw]);
+        if (EPI == 2) a = gelu_tanh(a);
+        if (EPI == 3) a = a / (1.f + expf(-a));
+        out[rw] = f2b(a);
+      }
+    }
+  }
+}
+
+template <int NORM>
+__global__ void gemv_swiglu_int4_kernel(
+    bf16* __restrict__ out, const unsigned char* __restrict__ Wg,
+    const unsigned* __restrict__ gqp, const unsigned char* __restrict__ Wu,
+    const unsigned* __restrict__ uqp, const bf16* __restrict__ x,
+    const bf16* __restrict__ nw, const bf16* __restrict__ nb, float eps,
+    int M, int K, int gelu_gate) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  __shared__ float red[8];
+  const int Kp = (K + 127) & ~127;
+  const int rowb = Kp >> 1;
+  const int ng = Kp >> 7;
+  bf16* xs = reinterpret_cast<bf16*>(smem);
+  float* gs = reinterpret_cast<float*>(smem + (size_t)Kp * sizeof(bf16));
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int waves_per_grid = gridDim.x * (blockDim.x >> 6);
+  const int row0 = blockIdx.x * (blockDim.x >> 6) + wave;
+
+  // prefetch across the staging barrier
+  i32x4_t gpre, upre;
+  const bool pre_ok = lane * 16 < rowb;
+  if (pre_ok) {
+    const size_t rw = (size_t)min(row0, M - 1);
+    gpre = load16_nt_u8(Wg + rw * rowb + lane * 16);
+    upre = load16_nt_u8(Wu + rw * rowb + lane * 16);
+  }
+
+  const float nscale = stage_x<NORM>(xs, x, nw, nb, K, eps, red);
+  stage_group_sums(xs, gs, K, Kp);
+
+  for (int row = row0; row < M; row += waves_per_grid) {
+    const unsigned char* grow = Wg + (size_t)row * rowb;
+    const unsigned char* urow = Wu + (size_t)row * rowb;
+    const unsigned* gq = gqp + (size_t)row * ng;
+    const unsigned* uq = uqp + (size_t)row * ng;
+    float ga = 0.f, ua = 0.f;
+    int istart = lane * 16;
+    if (row == row0 && pre_ok) {
+      const x32w xv = load_x32(xs + istart * 2);
+      const int g = istart >> 6;
+      const float gsum = gs[g];
+      ga += dot32_int4(gpre, xv, gq[g], gsum);
+      ua += dot32_int4(upre, xv, uq[g], gsum);
+      istart += 64 * 16;
+    }
+    for (int i = istart; i < rowb; i += 64 * 16) {
+      const i32x4_t gw = load16_nt_u8(grow + i);
+      const i32x4_t uw = load16_nt_u8(urow + i);
+      const x32w xv = load_x32(xs + i * 2);
+      const int g = i >> 6;
+      const float gsum = gs[g];
+      ga += dot32_int4(gw, xv, gq[g], gsum);
+      ua += dot32_int4(uw, xv, uq[g], gsum);
+    }
+    ga = wave_reduce_sum(ga) * nscale;
+    ua = wave_reduce_sum(ua) * nscale;
+    if (lane == 0) {
+      float act = gelu_gate ? gelu_tanh(ga) : ga / (1.f + expf(-ga));
+      out[row] = f2b(act * ua);
+    }
+  }
+}
+
 // SwiGLU pair GEMV: out[i] = silu(Wg_i . xn) * (Wu_i . xn), optional fused
 // pre-norm like gemv_kernel.  eidx/estride select an expert weight slab
 // from stacked [n_expert, M, K] tensors AT LAUNCH-REPLAY TIME (the index
@@ -3319,6 +3550,73 @@ void launch_gemv_swiglu_fp8(void* out, const void* Wg, const float* gscale,
     default: SW8_CASE(0);
   }
 #undef SW8_CASE
+}
+
+// LDS: Kp staged x (bf16) + one fp32 x-sum per 128-group
+static inline int int4_smem(int K) {
+  const int Kp = (K + 127) & ~127;
+  return Kp * (int)sizeof(bf16) + (Kp / 128) * (int)sizeof(float);
+}
+
+void launch_gemv_int4(void* out, const void* W, const void* qparams,
+                      const void* x, const void* bias, const void* res,
+                      const void* norm_w, const void* norm_b, float eps,
+                      int M, int K, int epilogue, int norm_kind, int rows,
+                      hipStream_t stream) {
+  const int smem = int4_smem(K);
+  if (rows == 0) rows = M >= 32768 ? 4 : (M > 8192 ? 2 : 1);
+  dim3 grid(gemv_grid(M, 4 * rows)), block(256);
+#define GEMV4_CASE1(E, N, R)                                                \
+  hipLaunchKernelGGL((gemv_int4_kernel<E, N, R>), grid, block, smem,        \
+                     stream, (bf16*)out, (const unsigned char*)W,           \
+                     (const unsigned*)qparams, (const bf16*)x,              \
+                     (const bf16*)bias, (const bf16*)res,                   \
+                     (const bf16*)norm_w, (const bf16*)norm_b, eps, M, K)
+#define GEMV4_CASE(E, N)                                                    \
+  do {                                                                      \
+    if (rows == 4) GEMV4_CASE1(E, N, 4);                                    \
+    else if (rows == 2) GEMV4_CASE1(E, N, 2);                               \
+    else GEMV4_CASE1(E, N, 1);                                              \
+  } while (0)
+  switch (epilogue * 4 + norm_kind) {
+    case 0: GEMV4_CASE(0, 0); break;
+    case 1: GEMV4_CASE(0, 1); break;
+    case 2: GEMV4_CASE(0, 2); break;
+    case 4: GEMV4_CASE(1, 0); break;
+    case 5: GEMV4_CASE(1, 1); break;
+    case 6: GEMV4_CASE(1, 2); break;
+    case 8: GEMV4_CASE(2, 0); break;
+    case 9: GEMV4_CASE(2, 1); break;
+    case 10: GEMV4_CASE(2, 2); break;
+    case 12: GEMV4_CASE(3, 0); break;
+    case 13: GEMV4_CASE(3, 1); break;
+    case 14: GEMV4_CASE(3, 2); break;
+    default: GEMV4_CASE(0, 0);
+  }
+#undef GEMV4_CASE
+#undef GEMV4_CASE1
+}
+
+void launch_gemv_swiglu_int4(void* out, const void* Wg, const void* gq,
+                             const void* Wu, const void* uq, const void* x,
+                             const void* norm_w, const void* norm_b,
+                             float eps, int M, int K, int gelu_gate,
+                             int norm_kind, hipStream_t stream) {
+  const int smem = int4_smem(K);
+  dim3 grid(gemv_grid(M, 4)), block(256);
+#define SW4_CASE(N)                                                         \
+  hipLaunchKernelGGL((gemv_swiglu_int4_kernel<N>), grid, block, smem,       \
+                     stream, (bf16*)out, (const unsigned char*)Wg,          \
+                     (const unsigned*)gq, (const unsigned char*)Wu,         \
+                     (const unsigned*)uq, (const bf16*)x,                   \
+                     (const bf16*)norm_w, (const bf16*)norm_b, eps, M, K,   \
+                     gelu_gate)
+  switch (norm_kind) {
+    case 1: SW4_CASE(1); break;
+    case 2: SW4_CASE(2); break;
+    default: SW4_CASE(0);
+  }
+#undef SW4_CASE
 }
 
 void launch_gemv_swiglu(void* out, const void* Wg, const void* Wu,

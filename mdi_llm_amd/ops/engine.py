@@ -27,7 +27,17 @@ from ..config import ModelConfig
 from ..models.model import KVCachePool
 from . import require_hip_ops
 
-__all__ = ["DecodeEngine", "engine_supported"]
+__all__ = ["DecodeEngine", "engine_supported", "clamp_attn_chunks"]
+
+# attn_combine_kernel keeps chunk weights in 4 registers x 64 lanes
+ATTN_MAX_CHUNKS = 256
+
+
+def clamp_attn_chunks(n_chunks: int) -> int:
+    """Split-S chunk count the attention kernels accept: a multiple of 4
+    (the split kernel stages q once per 4-wave block, so a block's waves
+    must share one kv head) in [4, 256] (the combine's weight registers)."""
+    return min(ATTN_MAX_CHUNKS, max(4, (int(n_chunks) // 4) * 4))
 
 
 def engine_supported(config: ModelConfig) -> bool:
@@ -232,7 +242,7 @@ class DecodeEngine:
         if n_chunks == 16:
             n_chunks = default_chunks
         n_chunks = int(os.environ.get("MDI_ATTN_CHUNKS", n_chunks))
-        n_chunks = max(4, (n_chunks // 4) * 4)  # block-shared q staging
+        n_chunks = clamp_attn_chunks(n_chunks)
         self.weight_dtype = os.environ.get("MDI_WEIGHT_DTYPE", "bf16")
         self.kv_dtype = os.environ.get("MDI_KV_DTYPE", "bf16")
         self.ops = require_hip_ops()

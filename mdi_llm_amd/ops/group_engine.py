@@ -25,7 +25,7 @@ import torch.nn.functional as F
 from ..config import ModelConfig
 from ..models.model import KVCachePool
 from . import require_hip_ops
-from .engine import _BlockWeights, engine_supported
+from .engine import _BlockWeights, clamp_attn_chunks, engine_supported
 
 __all__ = ["GroupDecodeEngine", "group_engine_supported"]
 
@@ -101,6 +101,7 @@ class GroupDecodeEngine:
         self.stage = stage
         self.kv_pool = kv_pool
         self.B = group_size
+        n_chunks = clamp_attn_chunks(n_chunks)
         self.n_chunks = n_chunks
         self.device = next(stage.parameters()).device
         self.is_starter = hasattr(stage, "lm_head")

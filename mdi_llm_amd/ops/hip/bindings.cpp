@@ -409,6 +409,13 @@ void attn_decode(torch::Tensor out, torch::Tensor part_o,
   const int qkv_dim = (int)(qkv.numel() / beff);
   const int qpk = qkv_dim / (n_kv * hs) - 2;
   const int n_head = n_kv * qpk;
+  // the split-S kernel stages q once per 4-wave block (needs n_chunks % 4
+  // == 0 so a block's waves share one (batch, kv head)) and the combine
+  // keeps chunk weights in 4 registers x 64 lanes (chunks >= 256 would be
+  // silently ignored)
+  TORCH_CHECK(n_chunks >= 4 && n_chunks % 4 == 0 && n_chunks <= 256,
+              "attn_decode: n_chunks must be a multiple of 4 in [4, 256], "
+              "got ", n_chunks);
   if (nb > 0) {
     TORCH_CHECK(pos.numel() >= nb && slot.numel() >= nb,
                 "pos/slot arrays too small for batch");

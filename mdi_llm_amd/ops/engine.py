@@ -162,12 +162,26 @@ class _BlockWeights:
             # stacked expert slabs: the router index (device memory)
             # offsets into these at graph-replay time
             self.gate_w = p(mlp.gate.weight)
-            self.fc1_w = torch.stack(
-                [p(e.fc_1.weight) for e in mlp.experts]).contiguous()
-            self.fc2_w = torch.stack(
-                [p(e.fc_2.weight) for e in mlp.experts]).contiguous()
-            self.mlp_proj_w = torch.stack(
-                [p(e.proj.weight) for e in mlp.experts]).contiguous()
+            # The stacked copies are shared between the engines built on
+            # one stage (single-sample + grouped): at Mixtral size a second
+            # set would not fit beside the first.  The cache is keyed by
+            # the expert parameters' storage and version counters, so
+            # weights loaded later are stacked afresh.
+            src = [w_ for e in mlp.experts
+                   for w_ in (e.fc_1.weight, e.fc_2.weight, e.proj.weight)]
+            try:
+                key = tuple((w_.data_ptr(), w_._version) for w_ in src)
+            except RuntimeError:  # inference tensors track no version
+                key = None
+            cached = getattr(mlp, "_hip_expert_slabs", None)
+            if key is None or cached is None or cached[0] != key:
+                slabs = tuple(
+                    torch.stack([p(getattr(e, n).weight)
+                                 for e in mlp.experts]).contiguous()
+                    for n in ("fc_1", "fc_2", "proj"))
+                cached = (key, slabs)
+                mlp._hip_expert_slabs = cached
+            self.fc1_w, self.fc2_w, self.mlp_proj_w = cached[1]
             self.mlp_proj_b = None
         elif config.mlp_class_name in ("LLaMAMLP", "GemmaMLP"):
             self.fc1_w = p(mlp.fc_1.weight)

@@ -13,6 +13,12 @@ Implementation: the skinny [B,K]x[K,M] projections go through hipBLASLt
 flash-decode with fused RoPE + KV-append, per-sample positions), sampling
 (radix top-k + gumbel) and embedding use the hand-written CDNA4 kernels.
 The whole group step is captured as one hipGraph per role.
+
+MoE stages (LLaMAMoE) keep the dense attention half and replace the MLP
+half with hand-written kernels: ``moe_route_group`` (top-k + softmax per
+token, expert-major row layout), ``moe_group_swiglu`` / ``moe_group_down``
+(MFMA GEMMs over the permuted rows; each touched expert's slabs are read
+once per step however many tokens chose it) and ``moe_group_combine``.
 """
 
 from __future__ import annotations
@@ -58,12 +64,31 @@ def _maybe_enable_tunableop(B: int) -> None:
         warnings.warn(f"TunableOp setup failed ({e}); using default GEMMs")
 
 
-def group_engine_supported(config: ModelConfig) -> bool:
+# the grouped MoE kernels keep one expert's gathered rows in LDS
+MOE_MAX_GROUP = 128
+
+
+def _moe_group_supported(config: ModelConfig) -> bool:
+    """Shapes the grouped MoE kernels launch on: both expert GEMMs need
+    K % 32 == 0 (MFMA k step) and M % 16 == 0 (row tile), and n_embd and
+    intermediate_size each play both roles (gate/up vs down)."""
+    k, n_e = config.n_expert_per_token, config.n_expert
     return (
-        engine_supported(config)
-        and config.norm_class_name == "RMSNorm"
-        and config.mlp_class_name in ("LLaMAMLP", "GemmaMLP")
+        1 <= k <= min(8, n_e)
+        and n_e <= 64
+        and config.n_embd % 32 == 0
+        and (config.intermediate_size or 0) > 0
+        and config.intermediate_size % 32 == 0
     )
+
+
+def group_engine_supported(config: ModelConfig) -> bool:
+    if not (engine_supported(config)
+            and config.norm_class_name == "RMSNorm"):
+        return False
+    if config.mlp_class_name == "LLaMAMoE":
+        return _moe_group_supported(config)
+    return config.mlp_class_name in ("LLaMAMLP", "GemmaMLP")
 
 
 class GroupDecodeEngine:
@@ -82,6 +107,11 @@ class GroupDecodeEngine:
         _maybe_enable_tunableop(group_size)
         if not group_engine_supported(cfg):
             raise ValueError(f"{cfg.name!r} unsupported by GroupDecodeEngine")
+        self.moe = cfg.mlp_class_name == "LLaMAMoE"
+        if self.moe and group_size > MOE_MAX_GROUP:
+            raise ValueError(
+                f"grouped MoE decode supports group_size <= {MOE_MAX_GROUP}"
+                f" (got {group_size})")
         # fp8 grouped GEMMs measured SLOWER than bf16 hipBLASLt on ROCm 7
         # (skinny-M _scaled_mm + dynamic-quant overhead): keep groups bf16.
         # fp8 weights remain available for B=1 decode (DecodeEngine).
@@ -143,6 +173,8 @@ class GroupDecodeEngine:
         # B=32 +0.2% noise, B=64 -2%).  Default OFF — a documented
         # measured refutation; MDI_MTILE=proj|all opts in.
         mt_env = os.environ.get("MDI_MTILE", "0")
+        if self.moe:
+            mt_env = "0"  # the expert GEMMs are their own kernels
         shapes_ok = (B in (16, 32, 64, 128)
                      and all(self._mtile_k_ok(B, k)
                              for k in (E, n_head * hs, I)))
@@ -158,6 +190,20 @@ class GroupDecodeEngine:
         if self.use_mtile:
             self.G = torch.zeros(B, I, **bf)
             self.U2 = torch.zeros(B, I, **bf)
+        if self.moe:
+            # routing + expert-major workspaces: static sizes (B*k rows),
+            # only the contents depend on the routing -> graph-stable
+            k, n_e = cfg.n_expert_per_token, cfg.n_expert
+            i32 = dict(device=dev, dtype=torch.int32)
+            self.moe_eidx = torch.zeros(B * k, **i32)
+            self.moe_escale = torch.zeros(B * k, device=dev,
+                                          dtype=torch.float32)
+            self.moe_count = torch.zeros(n_e, **i32)
+            self.moe_offset = torch.zeros(n_e + 1, **i32)
+            self.moe_perm = torch.zeros(B * k, **i32)
+            self.moe_inv = torch.zeros(B * k, **i32)
+            self.ACT = torch.zeros(B * k, I, **bf)
+            self.D = torch.zeros(B * k, E, device=dev, dtype=torch.float32)
         self.part_o = torch.zeros(B * n_head * n_chunks * hs, device=dev,
                                   dtype=torch.float32)
         self.part_ml = torch.zeros(B * n_head * n_chunks * 2, device=dev,
@@ -277,6 +323,10 @@ class GroupDecodeEngine:
             else:
                 a = X + F.linear(self.Y, w.proj_w, w.proj_b)
             hn = self._rms(a, w.norm2_w, self.HN)
+            if self.moe:
+                self._moe_mlp(hn, w, a)
+                X = self.X
+                continue
             if fp8:
                 gate = self._mm(hn, w.fc1_w8, w.fc1_s, w.fc1_w)
                 up = self._mm(hn, w.fc2_w8, w.fc2_s, w.fc2_w)
@@ -293,7 +343,30 @@ class GroupDecodeEngine:
                 X = torch.addmm(a, act, w.mlp_proj_w.t())
             else:
                 X = a + F.linear(act, w.mlp_proj_w, w.mlp_proj_b)
-        self.X.copy_(X)
+        if not self.moe:  # the MoE combine already wrote self.X
+            self.X.copy_(X)
+
+    def _moe_mlp(self, hn: torch.Tensor, w, a: torch.Tensor) -> None:
+        """self.X = a + sum_rank escale * expert(hn): device-side routing of
+        the whole group, then each touched expert's slabs streamed once
+        against all of its tokens (reference model.py:823-853 semantics).
+        `hn` is the bf16-rounded norm — it feeds the router exactly as in
+        the torch module and the single-sample engine, so near-tied
+        experts route the same way."""
+        ops = self.ops
+        k = self.config.n_expert_per_token
+        logits = F.linear(hn, w.gate_w)
+        ops.moe_route_group(self.moe_eidx, self.moe_escale, self.moe_count,
+                            self.moe_offset, self.moe_perm, self.moe_inv,
+                            logits, k)
+        ops.moe_group_swiglu(self.ACT, w.fc1_w, w.fc2_w, hn, self.moe_count,
+                             self.moe_offset, self.moe_perm, self.moe_escale,
+                             k)
+        ops.moe_group_down(self.D, w.mlp_proj_w, self.ACT, self.moe_count,
+                           self.moe_offset, self.B)
+        # a is never self.X (it is the proj GEMM's output), so the
+        # residual stream can land in place
+        ops.moe_group_combine(self.X, a, self.D, self.moe_inv, k)
 
     def _tail_seq(self) -> None:
         xn = self._rms(self.X, self.lnf_w, self.XN)
@@ -332,7 +405,10 @@ class GroupDecodeEngine:
     # pos/token tables and KV pool are per-slot and stay shared)
     _LANE_ATTRS = ("X", "XN", "HN", "QKV", "Y", "part_o", "part_ml",
                    "LOGITS", "sample_scratch", "tokens", "slots",
-                   "slots_long", "pos")
+                   "slots_long", "pos",
+                   # grouped MoE routing + expert-major workspaces
+                   "moe_eidx", "moe_escale", "moe_count", "moe_offset",
+                   "moe_perm", "moe_inv", "ACT", "D")
 
     def _set_lane(self, lane: int) -> None:
         for a, t_ in self._lane_bufs[lane].items():

@@ -332,6 +332,107 @@ void moe_gate_topk(torch::Tensor eidx, torch::Tensor escale,
                        logits.data_ptr(), n_e, (int)k, cur_stream());
 }
 
+inline void check_i32n(const torch::Tensor& t, const char* name,
+                       int64_t n) {
+  check_i32(t, name);
+  TORCH_CHECK(t.is_contiguous() && t.numel() == n, name, ": expected ", n,
+              " contiguous int32 elements");
+}
+
+void moe_route_group(torch::Tensor eidx, torch::Tensor escale,
+                     torch::Tensor count, torch::Tensor offset,
+                     torch::Tensor perm, torch::Tensor inv,
+                     torch::Tensor logits, int64_t k) {
+  check_bf16(logits, "logits");
+  TORCH_CHECK(logits.dim() == 2, "logits must be [B, n_expert]");
+  const int64_t B = logits.size(0), n_e = logits.size(1);
+  TORCH_CHECK(B >= 1 && B <= 128 && n_e >= 1 && n_e <= 64 && k >= 1 &&
+                  k <= 8 && k <= n_e,
+              "moe_route_group: B <= 128, n_e <= 64, 1 <= k <= min(8, n_e)");
+  check_i32n(eidx, "eidx", B * k);
+  check_f32(escale, "escale");
+  TORCH_CHECK(escale.numel() == B * k, "escale size");
+  check_i32n(count, "count", n_e);
+  check_i32n(offset, "offset", n_e + 1);
+  check_i32n(perm, "perm", B * k);
+  check_i32n(inv, "inv", B * k);
+  launch_moe_route_group(eidx.data_ptr<int>(), escale.data_ptr<float>(),
+                         count.data_ptr<int>(), offset.data_ptr<int>(),
+                         perm.data_ptr<int>(), inv.data_ptr<int>(),
+                         logits.data_ptr(), (int)B, (int)n_e, (int)k,
+                         cur_stream());
+}
+
+void moe_group_swiglu(torch::Tensor act, torch::Tensor Wg, torch::Tensor Wu,
+                      torch::Tensor X, torch::Tensor count,
+                      torch::Tensor offset, torch::Tensor perm,
+                      torch::Tensor escale, int64_t k) {
+  check_bf16(act, "act");
+  check_bf16(Wg, "Wg");
+  check_bf16(Wu, "Wu");
+  check_bf16(X, "X");
+  TORCH_CHECK(Wg.dim() == 3 && X.dim() == 2 && act.dim() == 2,
+              "moe_group_swiglu: Wg [n_e,M,K], X [B,K], act [B*k,M]");
+  const int64_t n_e = Wg.size(0), M = Wg.size(1), K = Wg.size(2);
+  const int64_t B = X.size(0);
+  TORCH_CHECK(Wu.sizes() == Wg.sizes(), "Wu shape");
+  TORCH_CHECK(X.size(1) == K && act.size(0) == B * k && act.size(1) == M,
+              "moe_group_swiglu: size mismatch");
+  check_i32n(count, "count", n_e);
+  check_i32n(offset, "offset", n_e + 1);
+  check_i32n(perm, "perm", B * k);
+  check_f32(escale, "escale");
+  TORCH_CHECK(escale.numel() == B * k, "escale size");
+  const int rc = launch_moe_group_gemm(
+      act.data_ptr(), Wg.data_ptr(), Wu.data_ptr(), X.data_ptr(),
+      count.data_ptr<int>(), offset.data_ptr<int>(), perm.data_ptr<int>(),
+      escale.data_ptr<float>(), (int)B, (int)n_e, (int)M, (int)K, (int)k, 1,
+      cur_stream());
+  TORCH_CHECK(rc == 0, "moe_group_swiglu: needs K % 32 == 0, M % 16 == 0, "
+                       "B <= 128, n_e <= 64, k <= 8");
+}
+
+void moe_group_down(torch::Tensor D, torch::Tensor Wd, torch::Tensor act,
+                    torch::Tensor count, torch::Tensor offset,
+                    int64_t n_tokens) {
+  check_f32(D, "D");
+  check_bf16(Wd, "Wd");
+  check_bf16(act, "act");
+  TORCH_CHECK(Wd.dim() == 3 && act.dim() == 2 && D.dim() == 2,
+              "moe_group_down: Wd [n_e,M,K], act [B*k,K], D [B*k,M]");
+  const int64_t n_e = Wd.size(0), M = Wd.size(1), K = Wd.size(2);
+  const int64_t R = act.size(0);
+  TORCH_CHECK(n_tokens >= 1 && R % n_tokens == 0,
+              "moe_group_down: rows must be n_tokens * k");
+  TORCH_CHECK(act.size(1) == K && D.size(0) == R && D.size(1) == M,
+              "moe_group_down: size mismatch");
+  check_i32n(count, "count", n_e);
+  check_i32n(offset, "offset", n_e + 1);
+  const int rc = launch_moe_group_gemm(
+      D.data_ptr(), Wd.data_ptr(), nullptr, act.data_ptr(),
+      count.data_ptr<int>(), offset.data_ptr<int>(), nullptr, nullptr,
+      (int)n_tokens, (int)n_e, (int)M, (int)K, (int)(R / n_tokens), 0,
+      cur_stream());
+  TORCH_CHECK(rc == 0, "moe_group_down: needs K % 32 == 0, M % 16 == 0, "
+                       "B <= 128, n_e <= 64, k <= 8");
+}
+
+void moe_group_combine(torch::Tensor out, torch::Tensor res, torch::Tensor D,
+                       torch::Tensor inv, int64_t k) {
+  check_bf16(out, "out");
+  check_bf16(res, "res");
+  check_f32(D, "D");
+  TORCH_CHECK(res.dim() == 2 && D.dim() == 2, "res [B,E], D [B*k,E]");
+  const int64_t B = res.size(0), E = res.size(1);
+  TORCH_CHECK(out.sizes() == res.sizes() && D.size(0) == B * k &&
+                  D.size(1) == E && E % 8 == 0 && k >= 1,
+              "moe_group_combine: size mismatch");
+  check_i32n(inv, "inv", B * k);
+  launch_moe_group_combine(out.data_ptr(), res.data_ptr(),
+                           D.data_ptr<float>(), inv.data_ptr<int>(), (int)B,
+                           (int)E, (int)k, cur_stream());
+}
+
 void embed(torch::Tensor out, torch::Tensor wte, torch::Tensor token,
            double scale) {
   check_bf16(out, "out");
@@ -715,6 +816,26 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_gate_topk", &moe_gate_topk,
         "MoE router: top-k experts + softmax weights over the k",
         py::arg("eidx"), py::arg("escale"), py::arg("logits"), py::arg("k"));
+  m.def("moe_route_group", &moe_route_group,
+        "grouped MoE router: per-token top-k + softmax and the "
+        "expert-major row layout (count/offset/perm/inv)",
+        py::arg("eidx"), py::arg("escale"), py::arg("count"),
+        py::arg("offset"), py::arg("perm"), py::arg("inv"),
+        py::arg("logits"), py::arg("k"));
+  m.def("moe_group_swiglu", &moe_group_swiglu,
+        "grouped MoE gate/up MFMA GEMM pair + SwiGLU * routing weight over "
+        "the permuted rows",
+        py::arg("act"), py::arg("Wg"), py::arg("Wu"), py::arg("X"),
+        py::arg("count"), py::arg("offset"), py::arg("perm"),
+        py::arg("escale"), py::arg("k"));
+  m.def("moe_group_down", &moe_group_down,
+        "grouped MoE down MFMA GEMM over the permuted rows (fp32 out)",
+        py::arg("D"), py::arg("Wd"), py::arg("act"), py::arg("count"),
+        py::arg("offset"), py::arg("n_tokens"));
+  m.def("moe_group_combine", &moe_group_combine,
+        "out[b] = res[b] + sum over ranks of the token's expert rows",
+        py::arg("out"), py::arg("res"), py::arg("D"), py::arg("inv"),
+        py::arg("k"));
   m.def("embed", &embed, "embedding row gather");
   m.def("rope_kv_append", &rope_kv_append,
         "RoPE on interleaved qkv + KV cache append");

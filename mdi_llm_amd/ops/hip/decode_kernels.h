@@ -68,6 +68,30 @@ void launch_swiglu_mul(void* out, const void* g, const void* u,
 void launch_moe_gate_topk(int* eidx, float* escale, const void* logits,
                           int n_e, int k, hipStream_t stream);
 
+// grouped MoE decode (B <= 128 tokens, n_e <= 64, k <= 8).  The B*k
+// (token, rank) pairs are numbered f = token*k + rank; permuted row s in
+// [offset[e], offset[e+1]) belongs to expert e and holds pair perm[s]
+// (ascending f inside an expert); inv[f] = s.
+void launch_moe_route_group(int* eidx, float* escale, int* count,
+                            int* offset, int* perm, int* inv,
+                            const void* logits, int B, int n_e, int k,
+                            hipStream_t stream);
+
+// expert GEMMs over the permuted rows, W* stacked [n_e, M, K] bf16.
+// swiglu != 0: out bf16 [B*k, M] = silu(x Wa^T) * (x Wb^T) * escale, x
+// gathered from X[B, K]; swiglu == 0: out fp32 [B*k, M] = X[s] Wa^T with
+// X[B*k, K].  K % 32 == 0, M % 16 == 0; returns -1 otherwise.
+int launch_moe_group_gemm(void* out, const void* Wa, const void* Wb,
+                          const void* X, const int* count, const int* offset,
+                          const int* perm, const float* escale, int Bsz,
+                          int n_e, int M, int K, int k_top, int swiglu,
+                          hipStream_t stream);
+
+// out[b] = res[b] + sum_rank D[inv[b*k + rank]] (fp32, rank order)
+void launch_moe_group_combine(void* out, const void* res, const float* D,
+                              const int* inv, int Bsz, int E, int k,
+                              hipStream_t stream);
+
 void launch_embed(void* out, const void* wte, const int* token, int n_embd,
                   float scale, hipStream_t stream);
 

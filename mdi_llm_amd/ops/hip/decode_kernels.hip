@@ -774,6 +774,375 @@ __global__ void moe_gate_topk_kernel(int* __restrict__ eidx,
 }
 
 // ---------------------------------------------------------------------------
+// Grouped (batched) MoE decode: B <= 128 tokens advance together, each
+// routed to k of n_e experts.  Three stages, all with static launch
+// geometry (only buffer CONTENTS are data-dependent, so the step stays one
+// hipGraph and never syncs with the host):
+//   moe_route_group   per-token top-k + softmax (moe_gate_topk_kernel
+//                     semantics) and the expert-major row layout
+//   moe_group_gemm    <SWIGLU>: ACT[s] = silu(x Wg^T) * (x Wu^T) * escale
+//                     <down>  : D[s]   = ACT[s] Wd^T          (fp32)
+//   moe_group_combine X_out[b] = res[b] + sum_rank D[inv[b,rank]]
+//
+// Layout: the B*k (token, rank) pairs are numbered f = token*k + rank.
+// Permuted row s in [offset[e], offset[e+1]) belongs to expert e and holds
+// pair perm[s]; inside an expert the rows ascend in f (token, then rank),
+// so the layout is a pure function of the logits.  inv[f] = s.
+// ---------------------------------------------------------------------------
+#define MOE_MAX_B 128
+#define MOE_MAX_TOPK 8
+#define MOE_MAX_E 64
+
+__global__ __launch_bounds__(1024) void moe_route_group_kernel(
+    int* __restrict__ eidx, float* __restrict__ escale,
+    int* __restrict__ count, int* __restrict__ offset,
+    int* __restrict__ perm, int* __restrict__ inv,
+    const bf16* __restrict__ logits, int B, int n_e, int k) {
+  __shared__ int sel[MOE_MAX_B * MOE_MAX_TOPK];
+  __shared__ int cnt_s[MOE_MAX_E];
+  __shared__ int off_s[MOE_MAX_E + 1];
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int nw = blockDim.x >> 6;
+
+  // ---- per-token top-k + softmax: one wave per token, lane = expert ----
+  for (int b = wave; b < B; b += nw) {
+    float cur = (lane < n_e) ? b2f(logits[b * n_e + lane]) : -1e30f;
+    float selv[MOE_MAX_TOPK];
+    int seli[MOE_MAX_TOPK];
+#pragma unroll
+    for (int j = 0; j < MOE_MAX_TOPK; ++j) {
+      if (j >= k) continue;
+      float m = cur;
+      int mi = lane;
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) {
+        const float om = __shfl_xor(m, off, 64);
+        const int oi = __shfl_xor(mi, off, 64);
+        if (om > m || (om == m && oi < mi)) {
+          m = om;
+          mi = oi;
+        }
+      }
+      selv[j] = m;
+      seli[j] = mi;
+      if (lane == mi) cur = -1e30f;
+    }
+    if (lane == 0) {
+      const float mx = selv[0];
+      float ssum = 0.f;
+      float ex[MOE_MAX_TOPK];
+#pragma unroll
+      for (int j = 0; j < MOE_MAX_TOPK; ++j) {
+        ex[j] = (j < k) ? __expf(selv[j] - mx) : 0.f;
+        ssum += ex[j];
+      }
+#pragma unroll
+      for (int j = 0; j < MOE_MAX_TOPK; ++j) {
+        if (j < k) {
+          eidx[b * k + j] = seli[j];
+          escale[b * k + j] = ex[j] / ssum;
+          sel[b * k + j] = seli[j];
+        }
+      }
+    }
+  }
+  __syncthreads();
+
+  // ---- expert-major layout: a wave owns an expert and walks the pairs in
+  // ascending f, 64 at a time; ballot + popcount give each hit its rank ---
+  const int n = B * k;
+  for (int e = wave; e < n_e; e += nw) {
+    int c = 0;
+    for (int f0 = 0; f0 < n; f0 += 64) {
+      const int f = f0 + lane;
+      const bool hit = f < n && sel[f] == e;
+      c += __popcll(__ballot(hit));
+    }
+    if (lane == 0) cnt_s[e] = c;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int run = 0;
+    for (int e = 0; e < n_e; ++e) {
+      off_s[e] = run;
+      run += cnt_s[e];
+    }
+    off_s[n_e] = run;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < n_e) count[threadIdx.x] = cnt_s[threadIdx.x];
+  if ((int)threadIdx.x <= n_e) offset[threadIdx.x] = off_s[threadIdx.x];
+  for (int e = wave; e < n_e; e += nw) {
+    int run = off_s[e];
+    for (int f0 = 0; f0 < n; f0 += 64) {
+      const int f = f0 + lane;
+      const bool hit = f < n && sel[f] == e;
+      const unsigned long long mask = __ballot(hit);
+      if (hit) {
+        const int s = run + __popcll(mask & ((1ull << lane) - 1ull));
+        perm[s] = f;
+        inv[f] = s;
+      }
+      run += __popcll(mask);
+    }
+  }
+}
+
+// Expert GEMMs.  Grid (M/16, n_e): a block owns 16 output rows of ONE
+// expert and returns before any weight load when that expert got no token.
+// Otherwise it streams its 16 x K weight rows from HBM exactly once (non-
+// temporal, straight into MFMA A-fragments, ring two K-chunks deep) and
+// multiplies them against ALL count[e] gathered token rows, which are
+// staged per K-chunk in LDS as the B operand (XOR swizzle of
+// mtile_gemm_kernel, same 16x16x32 fragment convention, 4 waves split K).
+// Rows count[e]..16*ceil(count[e]/16) of the last token tile are staged as
+// zeros and never written back.
+//
+// LDS: two X buffers of RB x KC bf16, RB = B rounded up to 16/32/64/128 and
+// KC = 512/512/256/128 -> 32 KB (RB=16) or 64 KB, plus 1 KB of row maps:
+// two blocks per CU fit the 160 KB of a gfx950 CU at every B <= 128.  The
+// K-reduce scratch ([2][4 waves][RB][16] fp32 <= 64 KB) overlays the X
+// buffers once the last chunk is consumed.
+// K % 32 == 0 (a wave skips the 32-wide steps past K), M % 16 == 0.
+template <int RB, bool SWIGLU>
+__global__ __launch_bounds__(256) void moe_group_gemm_kernel(
+    void* __restrict__ outp,            // SWIGLU: bf16 [nrows, M]; else fp32
+    const bf16* __restrict__ Wa,        // [n_e, M, K] gate (or down) slabs
+    const bf16* __restrict__ Wb,        // [n_e, M, K] up slabs (SWIGLU)
+    const bf16* __restrict__ X,         // SWIGLU: [B, K] tokens; else
+                                        // [nrows, K] permuted activations
+    const int* __restrict__ count, const int* __restrict__ offset,
+    const int* __restrict__ perm, const float* __restrict__ escale,
+    int M, int K, int k_top, int nrows) {
+  constexpr int KC = (RB <= 32) ? 512 : (RB <= 64 ? 256 : 128);
+  constexpr int BT = RB / 16;
+  constexpr int PRE = RB * KC / 8 / 256;
+  constexpr int SPC = KC / 4 / 32;
+  const int e = blockIdx.y;
+  const int cnt = min(count[e], RB);
+  const int off = offset[e];
+  if (cnt <= 0 || off < 0 || off >= nrows) return;
+
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  __shared__ int srow[RB];
+  __shared__ float sscale[RB];
+  bf16* xbuf0 = reinterpret_cast<bf16*>(smem);
+  bf16* xbuf1 = xbuf0 + RB * KC;
+  float* c_red = reinterpret_cast<float*>(smem);
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int row0 = (int)blockIdx.x * 16;
+  const int arow = lane & 15;
+  const int sub = lane >> 4;
+  const int koff = sub * 8;
+  const int nt = (cnt + 15) >> 4;       // token tiles in use
+  const int rows_used = nt * 16;
+  const int nch = (K + KC - 1) / KC;
+
+  // source row of each staged row (-1: padding -> zeros)
+  for (int r = tid; r < RB; r += 256) {
+    int src = -1;
+    float sc = 0.f;
+    const int s = off + r;
+    if (r < cnt && s < nrows) {
+      if (SWIGLU) {
+        const int f = min(max(perm[s], 0), nrows - 1);
+        src = f / k_top;
+        sc = escale[f];
+      } else {
+        src = s;
+      }
+    }
+    srow[r] = src;
+    sscale[r] = sc;
+  }
+  __syncthreads();
+
+  f32x4 acca[BT], accb[BT];
+#pragma unroll
+  for (int t = 0; t < BT; ++t) {
+    acca[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+    accb[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+
+  auto xload = [&](int kb, bf16x8 (&pre)[PRE]) {
+#pragma unroll
+    for (int u = 0; u < PRE; ++u) {
+      const int i = tid + u * 256;
+      const int r = i / (KC / 8);
+      const int k8 = (i - r * (KC / 8)) * 8;
+      bf16x8 v;
+      *reinterpret_cast<int4*>(v.v) = make_int4(0, 0, 0, 0);
+      if (r < rows_used && kb + k8 < K) {
+        const int src = srow[r];
+        if (src >= 0) v = load8(X + (size_t)src * K + kb + k8);
+      }
+      pre[u] = v;
+    }
+  };
+  auto xstore = [&](bf16* buf, bf16x8 (&pre)[PRE]) {
+#pragma unroll
+    for (int u = 0; u < PRE; ++u) {
+      const int i = tid + u * 256;
+      const int r = i / (KC / 8);
+      const int k8 = (i - r * (KC / 8)) * 8;
+      if (r < rows_used)
+        *reinterpret_cast<int4*>(&buf[x_swz<KC>(r, k8)]) =
+            *reinterpret_cast<int4*>(pre[u].v);
+    }
+  };
+
+  const size_t wofs = ((size_t)e * M + row0 + arow) * (size_t)K;
+  const bf16* wa = Wa + wofs;
+  const bf16* wb = SWIGLU ? Wb + wofs : nullptr;
+  const int q0 = wave * (KC / 4);
+  auto wload = [&](int ci, bf16x8 (&ra)[SPC], bf16x8 (&rb)[SPC]) {
+#pragma unroll
+    for (int s = 0; s < SPC; ++s) {
+      const int kk = ci * KC + q0 + s * 32;
+      if (kk < K) {
+        ra[s] = load8_nt(wa + kk + koff);
+        if (SWIGLU) rb[s] = load8_nt(wb + kk + koff);
+      }
+    }
+  };
+
+  // W rings first (the loads fly across the X staging), then X chunk 0
+  bf16x8 wra[2][SPC], wrb[2][SPC];
+#pragma unroll
+  for (int s = 0; s < SPC; ++s) {
+    *reinterpret_cast<int4*>(wra[0][s].v) = make_int4(0, 0, 0, 0);
+    wra[1][s] = wra[0][s];
+    wrb[0][s] = wra[0][s];
+    wrb[1][s] = wra[0][s];
+  }
+  wload(0, wra[0], wrb[0]);
+  if (1 < nch) wload(1, wra[1], wrb[1]);
+  {
+    bf16x8 pre[PRE];
+    xload(0, pre);
+    xstore(xbuf0, pre);
+  }
+  __syncthreads();
+
+  // ring slot and LDS buffer are compile-time per call (see
+  // mtile_gemm_kernel: a runtime-indexed ring spills to scratch)
+  auto chunk_body = [&](int ci, bf16x8 (&ra)[SPC], bf16x8 (&rb)[SPC],
+                        bf16* cur, bf16* nxt) {
+    bf16x8 pre[PRE];
+    const bool more = ci + 1 < nch;
+    if (more) xload((ci + 1) * KC, pre);
+#pragma unroll
+    for (int s = 0; s < SPC; ++s) {
+      const int kl = q0 + s * 32;
+      if (ci * KC + kl < K) {
+        const bf16x8_t wfa = *reinterpret_cast<const bf16x8_t*>(ra[s].v);
+        const bf16x8_t wfb = *reinterpret_cast<const bf16x8_t*>(rb[s].v);
+#pragma unroll
+        for (int t = 0; t < BT; ++t) {
+          if (t < nt) {
+            const bf16x8_t xf = *reinterpret_cast<const bf16x8_t*>(
+                &cur[x_swz<KC>(t * 16 + arow, kl + koff)]);
+            acca[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                wfa, xf, acca[t], 0, 0, 0);
+            if (SWIGLU)
+              accb[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                  wfb, xf, accb[t], 0, 0, 0);
+          }
+        }
+      }
+    }
+    if (ci + 2 < nch) wload(ci + 2, ra, rb);
+    if (more) xstore(nxt, pre);
+    __syncthreads();
+  };
+  for (int ci = 0; ci < nch; ci += 2) {
+    chunk_body(ci, wra[0], wrb[0], xbuf0, xbuf1);
+    if (ci + 1 < nch) chunk_body(ci + 1, wra[1], wrb[1], xbuf1, xbuf0);
+  }
+
+  // ---- intra-block K reduce through LDS + epilogue ----------------------
+  // c_red[mat][wave][col][16 rows], rows rotated by col so that both the
+  // fragment writes (lanes vary col) and the row-fastest reads spread
+  // over the banks
+  constexpr int CW = RB * 16;  // floats per (mat, wave)
+#pragma unroll
+  for (int t = 0; t < BT; ++t) {
+    if (t < nt) {
+      const int c = t * 16 + arow;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int idx = wave * CW + c * 16 + ((sub * 4 + r + c) & 15);
+        c_red[idx] = acca[t][r];
+        if (SWIGLU) c_red[4 * CW + idx] = accb[t][r];
+      }
+    }
+  }
+  __syncthreads();
+  for (int i = tid; i < rows_used * 16; i += 256) {
+    const int c = i >> 4;
+    const int r = i & 15;
+    if (c >= cnt) continue;            // padding rows are never written
+    const int s = off + c;
+    if (s >= nrows) continue;
+    const int idx = c * 16 + ((r + c) & 15);
+    const float a = c_red[idx] + c_red[CW + idx] + c_red[2 * CW + idx] +
+                    c_red[3 * CW + idx];
+    const size_t o = (size_t)s * M + row0 + r;
+    if (SWIGLU) {
+      const float* cu = c_red + 4 * CW;
+      const float u = cu[idx] + cu[CW + idx] + cu[2 * CW + idx] +
+                      cu[3 * CW + idx];
+      const float act = a / (1.f + expf(-a));
+      // routing weight in fp32 before the bf16 rounding (as gemv_swiglu)
+      reinterpret_cast<bf16*>(outp)[o] = f2b(act * u * sscale[c]);
+    } else {
+      reinterpret_cast<float*>(outp)[o] = a;
+    }
+  }
+}
+
+// X_out[b] = res[b] + sum_{rank} D[inv[b*k + rank]], fp32, ranks in order
+// 0..k-1: a token's result does not depend on who shares its group.
+// out may alias res (pure elementwise).
+__global__ void moe_group_combine_kernel(bf16* __restrict__ out,
+                                         const bf16* __restrict__ res,
+                                         const float* __restrict__ D,
+                                         const int* __restrict__ inv,
+                                         int E, int k, int nrows) {
+  const int b = blockIdx.y;
+  const int i = ((int)blockIdx.x * 256 + (int)threadIdx.x) * 8;
+  if (i >= E) return;
+  bf16x8 rv = load8(res + (size_t)b * E + i);
+  float acc[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc[j] = b2f(rv.v[j]);
+  for (int rk = 0; rk < k; ++rk) {
+    const int s = inv[b * k + rk];
+    if (s < 0 || s >= nrows) continue;
+    const float4 d0 = *reinterpret_cast<const float4*>(D + (size_t)s * E + i);
+    const float4 d1 =
+        *reinterpret_cast<const float4*>(D + (size_t)s * E + i + 4);
+    acc[0] += d0.x;
+    acc[1] += d0.y;
+    acc[2] += d0.z;
+    acc[3] += d0.w;
+    acc[4] += d1.x;
+    acc[5] += d1.y;
+    acc[6] += d1.z;
+    acc[7] += d1.w;
+  }
+  bf16x8 o;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) o.v[j] = f2b(acc[j]);
+  *reinterpret_cast<int4*>(out + (size_t)b * E + i) =
+      *reinterpret_cast<const int4*>(o.v);
+}
+
+// ---------------------------------------------------------------------------
 // FP8 (OCP e4m3) weight variants: W stored as fp8 with one fp32 scale per
 // output row (absmax/448 quantization).  Halves the decode weight stream;
 // dequant via the gfx950 packed converts (v_cvt_pk_f32_fp8).
@@ -3654,6 +4023,64 @@ void launch_moe_gate_topk(int* eidx, float* escale, const void* logits,
                           int n_e, int k, hipStream_t stream) {
   hipLaunchKernelGGL(moe_gate_topk_kernel, dim3(1), dim3(64), 0, stream,
                      eidx, escale, (const bf16*)logits, n_e, k);
+}
+
+void launch_moe_route_group(int* eidx, float* escale, int* count,
+                            int* offset, int* perm, int* inv,
+                            const void* logits, int B, int n_e, int k,
+                            hipStream_t stream) {
+  hipLaunchKernelGGL(moe_route_group_kernel, dim3(1), dim3(1024), 0, stream,
+                     eidx, escale, count, offset, perm, inv,
+                     (const bf16*)logits, B, n_e, k);
+}
+
+// swiglu != 0: out = bf16 ACT[B*k, M] from tokens X[B, K];
+// swiglu == 0: out = fp32 D[B*k, M] from permuted rows X[B*k, K].
+// Returns -1 when the shape has no instantiation.
+int launch_moe_group_gemm(void* out, const void* Wa, const void* Wb,
+                          const void* X, const int* count, const int* offset,
+                          const int* perm, const float* escale, int Bsz,
+                          int n_e, int M, int K, int k_top, int swiglu,
+                          hipStream_t stream) {
+  if (M % 16 != 0 || K % 32 != 0 || Bsz < 1 || Bsz > MOE_MAX_B ||
+      n_e < 1 || n_e > MOE_MAX_E || k_top < 1 || k_top > MOE_MAX_TOPK)
+    return -1;
+  const dim3 grid(M / 16, n_e);
+  const int nrows = Bsz * k_top;
+#define MOE_CASE1(RBB, KCC, SW)                                             \
+  {                                                                         \
+    static bool attr_set = false;                                           \
+    if (!attr_set) {                                                        \
+      (void)hipFuncSetAttribute(                                            \
+          reinterpret_cast<const void*>(&moe_group_gemm_kernel<RBB, SW>),   \
+          hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);           \
+      attr_set = true;                                                      \
+    }                                                                       \
+    hipLaunchKernelGGL((moe_group_gemm_kernel<RBB, SW>), grid, dim3(256),   \
+                       (size_t)2 * RBB * KCC * 2, stream, out,              \
+                       (const bf16*)Wa, (const bf16*)Wb, (const bf16*)X,    \
+                       count, offset, perm, escale, M, K, k_top, nrows);    \
+    return 0;                                                               \
+  }
+#define MOE_CASE(RBB, KCC)                                                  \
+  if (Bsz <= RBB) {                                                         \
+    if (swiglu) MOE_CASE1(RBB, KCC, true) else MOE_CASE1(RBB, KCC, false)   \
+  }
+  MOE_CASE(16, 512)
+  MOE_CASE(32, 512)
+  MOE_CASE(64, 256)
+  MOE_CASE(128, 128)
+#undef MOE_CASE
+#undef MOE_CASE1
+  return -1;
+}
+
+void launch_moe_group_combine(void* out, const void* res, const float* D,
+                              const int* inv, int Bsz, int E, int k,
+                              hipStream_t stream) {
+  const dim3 grid((E / 8 + 255) / 256, Bsz);
+  hipLaunchKernelGGL(moe_group_combine_kernel, grid, dim3(256), 0, stream,
+                     (bf16*)out, (const bf16*)res, D, inv, E, k, Bsz * k);
 }
 
 void launch_embed(void* out, const void* wte, const int* token, int n_embd,

@@ -72,6 +72,41 @@ def bench_swiglu():
         print(f"{name}: {us:.1f} us  {gb/(us*1e-6):.2f} TB/s")
 
 
+def bench_moe_group():
+    """Grouped MoE expert GEMMs at the Mixtral shape (one layer: 8 experts,
+    top-2).  TB/s counts the slabs of the experts that got a token."""
+    E, I, n_e, k = 4096, 14336, 8, 2
+    Wg = torch.randn(n_e, I, E, device=DEV).to(torch.bfloat16) * 0.02
+    Wu = torch.randn(n_e, I, E, device=DEV).to(torch.bfloat16) * 0.02
+    Wd = torch.randn(n_e, E, I, device=DEV).to(torch.bfloat16) * 0.02
+    i32 = dict(device=DEV, dtype=torch.int32)
+    for B in (1, 8, 32, 128):
+        X = torch.randn(B, E, device=DEV).to(torch.bfloat16)
+        logits = torch.randn(B, n_e, device=DEV).to(torch.bfloat16)
+        eidx = torch.zeros(B * k, **i32)
+        escale = torch.zeros(B * k, device=DEV)
+        count = torch.zeros(n_e, **i32)
+        offset = torch.zeros(n_e + 1, **i32)
+        perm = torch.zeros(B * k, **i32)
+        inv = torch.zeros(B * k, **i32)
+        ACT = torch.zeros(B * k, I, device=DEV, dtype=torch.bfloat16)
+        D = torch.zeros(B * k, E, device=DEV)
+        out = torch.zeros(B, E, device=DEV, dtype=torch.bfloat16)
+        us_r = timeit(lambda: ops.moe_route_group(
+            eidx, escale, count, offset, perm, inv, logits, k))
+        touched = int((count > 0).sum())
+        us_s = timeit(lambda: ops.moe_group_swiglu(
+            ACT, Wg, Wu, X, count, offset, perm, escale, k))
+        us_d = timeit(lambda: ops.moe_group_down(D, Wd, ACT, count, offset,
+                                                 B))
+        us_c = timeit(lambda: ops.moe_group_combine(out, X, D, inv, k))
+        tb = touched * I * E * 2 / 1e12
+        print(f"moe_group B={B:3d} ({touched} experts): route {us_r:5.1f} us"
+              f" | swiglu {us_s:7.1f} us {2*tb/(us_s*1e-6):5.2f} TB/s"
+              f" | down {us_d:7.1f} us {tb/(us_d*1e-6):5.2f} TB/s"
+              f" | combine {us_c:5.1f} us")
+
+
 def bench_attn():
     import math
     n_kv, qpk, hs = 8, 4, 128
@@ -124,5 +159,6 @@ if __name__ == "__main__":
     torch.manual_seed(0)
     bench_gemv()
     bench_swiglu()
+    bench_moe_group()
     bench_attn()
     bench_sampling()

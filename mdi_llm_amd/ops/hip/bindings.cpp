@@ -31,12 +31,62 @@ inline void check_i32(const torch::Tensor& t, const char* name) {
   TORCH_CHECK(t.scalar_type() == torch::kInt32, name, " must be int32");
 }
 
+// Shared GEMV argument checks.  Nothing checks a launch result, so a
+// launch that cannot succeed would return stale output: refuse it here.
+inline void check_gemv_dims(int64_t M, int64_t K, int64_t epilogue,
+                            int64_t norm_kind) {
+  TORCH_CHECK(M > 0 && K > 0, "empty GEMV");
+  TORCH_CHECK(epilogue >= 0 && epilogue <= 3, "epilogue must be 0..3");
+  TORCH_CHECK(norm_kind >= 0 && norm_kind <= 2, "norm_kind must be 0..2");
+}
+
+// the staged kernels keep x (K bf16) in dynamic LDS; 64 KiB is what a
+// launch gets without opting in to more
+inline void check_staged_lds(int64_t K) {
+  TORCH_CHECK(K * 2 <= 64 * 1024,
+              "K too large for the staged GEMV (x must fit 64 KiB of LDS)");
+}
+
+// optional bf16 vector of exactly n elements -> pointer (or nullptr)
+inline const void* opt_bf16_vec(const c10::optional<torch::Tensor>& t,
+                                int64_t n, const char* name) {
+  if (!t.has_value()) return nullptr;
+  check_bf16(*t, name);
+  TORCH_CHECK(t->numel() == n, name, " size");
+  return t->data_ptr();
+}
+
+struct NormPtrs {
+  const void* w = nullptr;
+  const void* b = nullptr;
+};
+
+inline NormPtrs check_norm(const c10::optional<torch::Tensor>& norm_w,
+                           const c10::optional<torch::Tensor>& norm_b,
+                           int64_t norm_kind, int64_t K) {
+  NormPtrs p;
+  if (norm_kind != 0) {
+    TORCH_CHECK(norm_w.has_value(), "norm_w required with norm_kind");
+    p.w = opt_bf16_vec(norm_w, K, "norm_w");
+    p.b = opt_bf16_vec(norm_b, K, "norm_b");
+  }
+  return p;
+}
+
+inline void check_fp8_weight(const torch::Tensor& W, int64_t M, int64_t K,
+                             const char* name) {
+  TORCH_CHECK(W.is_cuda() && W.element_size() == 1 && W.is_contiguous(),
+              name, " must be contiguous fp8/uint8 on GPU");
+  TORCH_CHECK(W.numel() == M * K, name, " shape mismatch");
+}
+
 void rmsnorm(torch::Tensor out, torch::Tensor x, torch::Tensor w,
              double eps) {
   check_bf16(out, "out");
   check_bf16(x, "x");
   check_bf16(w, "w");
   const int n = (int)w.numel();
+  TORCH_CHECK(n > 0 && x.numel() > 0, "empty rmsnorm");
   const int nb = (int)(x.numel() / n);
   TORCH_CHECK(n % 8 == 0, "n must be a multiple of 8");
   TORCH_CHECK(x.numel() == (int64_t)nb * n && out.numel() == x.numel(),
@@ -51,12 +101,10 @@ void layernorm(torch::Tensor out, torch::Tensor x, torch::Tensor w,
   check_bf16(x, "x");
   check_bf16(w, "w");
   const int n = (int)x.numel();
+  TORCH_CHECK(n > 0, "empty layernorm");
   TORCH_CHECK(n % 8 == 0, "n must be a multiple of 8");
-  const void* bp = nullptr;
-  if (b.has_value()) {
-    check_bf16(*b, "b");
-    bp = b->data_ptr();
-  }
+  TORCH_CHECK(w.numel() == n && out.numel() == n, "size mismatch");
+  const void* bp = opt_bf16_vec(b, n, "b");
   launch_layernorm(out.data_ptr(), x.data_ptr(), w.data_ptr(), bp, n,
                    (float)eps, cur_stream());
 }
@@ -72,9 +120,11 @@ void gemv(torch::Tensor out, torch::Tensor W, torch::Tensor x,
   check_bf16(x, "x");
   const int K = (int)x.numel();
   const int M = (int)out.numel();
+  check_gemv_dims(M, K, epilogue, norm_kind);
   const int* eip = nullptr;
   if (eidx.has_value()) {
     check_i32(*eidx, "eidx");
+    TORCH_CHECK(eidx->numel() > 0, "eidx is empty");
     TORCH_CHECK(norm_kind != 2, "expert indirection: no LayerNorm");
     TORCH_CHECK(W.numel() % ((int64_t)M * K) == 0, "stacked W shape");
     eip = eidx->data_ptr<int>();
@@ -82,29 +132,12 @@ void gemv(torch::Tensor out, torch::Tensor W, torch::Tensor x,
     TORCH_CHECK(W.numel() == (int64_t)M * K, "W shape mismatch");
   }
   TORCH_CHECK(K % 8 == 0, "K must be a multiple of 8");
-  const void* bp = nullptr;
-  const void* rp = nullptr;
-  const void* nwp = nullptr;
-  const void* nbp = nullptr;
-  if (bias.has_value()) {
-    check_bf16(*bias, "bias");
-    TORCH_CHECK(bias->numel() == M, "bias size");
-    bp = bias->data_ptr();
-  }
-  if (res.has_value()) {
-    check_bf16(*res, "res");
-    TORCH_CHECK(res->numel() == M, "res size");
-    rp = res->data_ptr();
-  }
-  if (norm_kind != 0) {
-    TORCH_CHECK(norm_w.has_value(), "norm_w required with norm_kind");
-    check_bf16(*norm_w, "norm_w");
-    nwp = norm_w->data_ptr();
-    if (norm_b.has_value()) {
-      check_bf16(*norm_b, "norm_b");
-      nbp = norm_b->data_ptr();
-    }
-  }
+  if (norm_kind == 2) check_staged_lds(K);  // 0/1 run the direct kernels
+  const void* bp = opt_bf16_vec(bias, M, "bias");
+  const void* rp = opt_bf16_vec(res, M, "res");
+  const NormPtrs np = check_norm(norm_w, norm_b, norm_kind, K);
+  const void* nwp = np.w;
+  const void* nbp = np.b;
   launch_gemv(out.data_ptr(), W.data_ptr(), x.data_ptr(), bp, rp, nwp, nbp,
               (float)eps, M, K, (int)epilogue, (int)norm_kind, (int)rows,
               eip, (long long)estride, cur_stream());
@@ -119,24 +152,18 @@ void gemv_fp8(torch::Tensor out, torch::Tensor W, torch::Tensor wscale,
   check_bf16(out, "out");
   check_bf16(x, "x");
   check_f32(wscale, "wscale");
-  TORCH_CHECK(W.is_cuda() && W.element_size() == 1 && W.is_contiguous(),
-              "W must be contiguous fp8/uint8 on GPU");
   const int K = (int)x.numel();
   const int M = (int)out.numel();
-  TORCH_CHECK(W.numel() == (int64_t)M * K, "W shape mismatch");
+  check_gemv_dims(M, K, epilogue, norm_kind);
+  check_fp8_weight(W, M, K, "W");
   TORCH_CHECK(K % 16 == 0, "K must be a multiple of 16 for fp8 weights");
   TORCH_CHECK(wscale.numel() == M, "wscale size");
-  const void* bp = nullptr;
-  const void* rp = nullptr;
-  const void* nwp = nullptr;
-  const void* nbp = nullptr;
-  if (bias.has_value()) { check_bf16(*bias, "bias"); bp = bias->data_ptr(); }
-  if (res.has_value()) { check_bf16(*res, "res"); rp = res->data_ptr(); }
-  if (norm_kind != 0) {
-    check_bf16(*norm_w, "norm_w");
-    nwp = norm_w->data_ptr();
-    if (norm_b.has_value()) { check_bf16(*norm_b, "norm_b"); nbp = norm_b->data_ptr(); }
-  }
+  check_staged_lds(K);
+  const void* bp = opt_bf16_vec(bias, M, "bias");
+  const void* rp = opt_bf16_vec(res, M, "res");
+  const NormPtrs np = check_norm(norm_w, norm_b, norm_kind, K);
+  const void* nwp = np.w;
+  const void* nbp = np.b;
   launch_gemv_fp8(out.data_ptr(), W.data_ptr(), wscale.data_ptr<float>(),
                   x.data_ptr(), bp, rp, nwp, nbp, (float)eps, M, K,
                   (int)epilogue, (int)norm_kind, (int)rows, cur_stream());
@@ -152,18 +179,18 @@ void gemv_swiglu_fp8(torch::Tensor out, torch::Tensor Wg,
   check_bf16(x, "x");
   check_f32(gscale, "gscale");
   check_f32(uscale, "uscale");
-  TORCH_CHECK(Wg.element_size() == 1 && Wu.element_size() == 1,
-              "fp8 weights must be 1-byte");
   const int K = (int)x.numel();
   const int M = (int)out.numel();
+  check_gemv_dims(M, K, 0, norm_kind);
+  check_fp8_weight(Wg, M, K, "Wg");
+  check_fp8_weight(Wu, M, K, "Wu");
   TORCH_CHECK(K % 16 == 0, "K must be a multiple of 16 for fp8 weights");
-  const void* nwp = nullptr;
-  const void* nbp = nullptr;
-  if (norm_kind != 0) {
-    check_bf16(*norm_w, "norm_w");
-    nwp = norm_w->data_ptr();
-    if (norm_b.has_value()) { check_bf16(*norm_b, "norm_b"); nbp = norm_b->data_ptr(); }
-  }
+  TORCH_CHECK(gscale.numel() == M && uscale.numel() == M,
+              "gscale/uscale size");
+  check_staged_lds(K);
+  const NormPtrs np = check_norm(norm_w, norm_b, norm_kind, K);
+  const void* nwp = np.w;
+  const void* nbp = np.b;
   launch_gemv_swiglu_fp8(out.data_ptr(), Wg.data_ptr(),
                          gscale.data_ptr<float>(), Wu.data_ptr(),
                          uscale.data_ptr<float>(), x.data_ptr(), nwp, nbp,
@@ -273,10 +300,12 @@ void gemv_swiglu(torch::Tensor out, torch::Tensor Wg, torch::Tensor Wu,
   check_bf16(x, "x");
   const int K = (int)x.numel();
   const int M = (int)out.numel();
+  check_gemv_dims(M, K, 0, norm_kind);
   const int* eip = nullptr;
   const float* esp = nullptr;
   if (eidx.has_value()) {
     check_i32(*eidx, "eidx");
+    TORCH_CHECK(eidx->numel() > 0, "eidx is empty");
     TORCH_CHECK(Wg.numel() % ((int64_t)M * K) == 0 &&
                     Wu.numel() % ((int64_t)M * K) == 0,
                 "stacked weight shape");
@@ -287,20 +316,14 @@ void gemv_swiglu(torch::Tensor out, torch::Tensor Wg, torch::Tensor Wu,
   }
   if (escale.has_value()) {
     check_f32(*escale, "escale");
+    TORCH_CHECK(escale->numel() > 0, "escale is empty");
     esp = escale->data_ptr<float>();
   }
   TORCH_CHECK(K % 8 == 0, "K must be a multiple of 8");
-  const void* nwp = nullptr;
-  const void* nbp = nullptr;
-  if (norm_kind != 0) {
-    TORCH_CHECK(norm_w.has_value(), "norm_w required with norm_kind");
-    check_bf16(*norm_w, "norm_w");
-    nwp = norm_w->data_ptr();
-    if (norm_b.has_value()) {
-      check_bf16(*norm_b, "norm_b");
-      nbp = norm_b->data_ptr();
-    }
-  }
+  check_staged_lds(K);
+  const NormPtrs np = check_norm(norm_w, norm_b, norm_kind, K);
+  const void* nwp = np.w;
+  const void* nbp = np.b;
   launch_gemv_swiglu(out.data_ptr(), Wg.data_ptr(), Wu.data_ptr(),
                      x.data_ptr(), nwp, nbp, (float)eps, M, K,
                      gelu_gate ? 1 : 0, (int)norm_kind, eip,

@@ -12,8 +12,8 @@ into the modules instead — gptserver.py:975-978).
 Supported natively: RMSNorm/LayerNorm, rope/learned positions, GQA
 attention (head_size multiple of 32, head_size*q_per_kv >= 64), LLaMA
 (SwiGLU) / Gemma / GPT-NeoX MLPs, sequential and parallel residual.
-MoE decodes natively (device-side routing); fp8+MoE and int4+MoE are
-refused.
+MoE decodes natively (device-side routing), also with fp8 expert slabs
+(the router weight stays bf16); int4+MoE is refused.
 """
 
 from __future__ import annotations
@@ -65,6 +65,19 @@ def quantize_fp8_rowwise(w: torch.Tensor):
     s = (wf.abs().amax(dim=1).clamp(min=1e-12) / 448.0).float()
     q = (wf / s[:, None]).to(torch.float8_e4m3fn)
     return q.contiguous(), s.contiguous()
+
+
+def quantize_fp8_slab(slab: torch.Tensor):
+    """Stacked expert slab bf16 [n_e,M,K] -> (fp8 e4m3 [n_e,M,K], fp32
+    scales [n_e,M]); expert e is quantize_fp8_rowwise(slab[e]) bit for bit
+    (one expert at a time: the fp32 temporaries stay one expert large)."""
+    assert slab.dim() == 3
+    q = torch.empty(slab.shape, dtype=torch.float8_e4m3fn,
+                    device=slab.device)
+    s = torch.empty(slab.shape[:2], dtype=torch.float32, device=slab.device)
+    for e in range(slab.size(0)):
+        q[e], s[e] = quantize_fp8_rowwise(slab[e])
+    return q, s
 
 
 INT4_GROUP = 128
@@ -173,6 +186,7 @@ class _BlockWeights:
                 key = tuple((w_.data_ptr(), w_._version) for w_ in src)
             except RuntimeError:  # inference tensors track no version
                 key = None
+            self._mlp, self._slab_key = mlp, key
             cached = getattr(mlp, "_hip_expert_slabs", None)
             if key is None or cached is None or cached[0] != key:
                 slabs = tuple(
@@ -194,12 +208,30 @@ class _BlockWeights:
             self.mlp_proj_w = p(mlp.proj.weight)
             self.mlp_proj_b = p(mlp.proj.bias)
 
+    def quantize_fp8_experts(self) -> None:
+        """MoE: attach fp8 copies + [n_e, M] row scales of the three expert
+        slabs.  Cached on the mlp module under the key of the bf16 slabs
+        (see __init__), so the engines built on one stage share one copy
+        and weights loaded later are quantized afresh.  The bf16 slabs
+        stay (prefill and the torch path read them) and the router weight
+        gets no fp8 twin: routing must see what the torch module sees."""
+        mlp, key = self._mlp, self._slab_key
+        cached = getattr(mlp, "_hip_expert_slabs_fp8", None)
+        if key is None or cached is None or cached[0] != key:
+            q = tuple(t for w_ in (self.fc1_w, self.fc2_w, self.mlp_proj_w)
+                      for t in quantize_fp8_slab(w_))
+            cached = (key, q)
+            mlp._hip_expert_slabs_fp8 = cached
+        (self.fc1_w8, self.fc1_s, self.fc2_w8, self.fc2_s,
+         self.mlp_proj_w8, self.mlp_proj_s) = cached[1]
+
     def quantize_fp8(self, config) -> None:
         """Attach fp8 copies + per-row scales for the decode GEMVs."""
-        if config.mlp_class_name == "LLaMAMoE":
-            raise ValueError("fp8 weights are not supported for MoE stages")
         self.attn_w8, self.attn_s = quantize_fp8_rowwise(self.attn_w)
         self.proj_w8, self.proj_s = quantize_fp8_rowwise(self.proj_w)
+        if config.mlp_class_name == "LLaMAMoE":
+            self.quantize_fp8_experts()
+            return
         self.mlp_proj_w8, self.mlp_proj_s = quantize_fp8_rowwise(
             self.mlp_proj_w)
         if config.mlp_class_name in ("LLaMAMLP", "GemmaMLP"):
@@ -282,6 +314,13 @@ class DecodeEngine:
         self.int4 = (self.weight_dtype == "int4"
                      and self.device.type == "cuda")
         if self.fp8:
+            if cfg.mlp_class_name == "LLaMAMoE" and (
+                    cfg.n_embd % 16 or cfg.intermediate_size % 16):
+                # gemv_fp8 / gemv_swiglu_fp8 stream 16 fp8 per lane
+                raise ValueError(
+                    f"fp8 expert weights need n_embd ({cfg.n_embd}) and "
+                    f"intermediate_size ({cfg.intermediate_size}) to be "
+                    f"multiples of 16 ({cfg.name!r})")
             for w in self.blocks:
                 w.quantize_fp8(cfg)
         if self.int4:
@@ -578,14 +617,25 @@ class DecodeEngine:
             out = self.m_out if cfg.parallel_residual else self.x
             res_j = res
             for j in range(cfg.n_expert_per_token):
+                ej = self.moe_eidx[j:j + 1]
+                if self.fp8:
+                    ops.gemv_swiglu_fp8(self.act, w.fc1_w8, w.fc1_s,
+                                        w.fc2_w8, w.fc2_s, self.xn, False,
+                                        None, None, 0, eps, eidx=ej,
+                                        estride=I * E,
+                                        escale=self.moe_escale[j:j + 1])
+                    ops.gemv_fp8(out, w.mlp_proj_w8, w.mlp_proj_s, self.act,
+                                 None, res_j, 1, None, None, 0, eps,
+                                 self._r_down, eidx=ej, estride=E * I)
+                    res_j = out
+                    continue
                 ops.gemv_swiglu(self.act, w.fc1_w, w.fc2_w, self.xn, False,
-                                None, None, 0, eps,
-                                eidx=self.moe_eidx[j:j + 1],
+                                None, None, 0, eps, eidx=ej,
                                 estride=I * E,
                                 escale=self.moe_escale[j:j + 1])
                 ops.gemv(out, w.mlp_proj_w, self.act, None, res_j, 1,
                          None, None, 0, eps, self._r_down,
-                         eidx=self.moe_eidx[j:j + 1], estride=E * I)
+                         eidx=ej, estride=E * I)
                 res_j = out
             return
         if cfg.mlp_class_name in ("LLaMAMLP", "GemmaMLP"):

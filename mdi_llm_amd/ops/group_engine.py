@@ -19,6 +19,9 @@ half with hand-written kernels: ``moe_route_group`` (top-k + softmax per
 token, expert-major row layout), ``moe_group_swiglu`` / ``moe_group_down``
 (MFMA GEMMs over the permuted rows; each touched expert's slabs are read
 once per step however many tokens chose it) and ``moe_group_combine``.
+With MDI_WEIGHT_DTYPE=fp8 the expert GEMMs read fp8 slabs
+(``moe_group_swiglu_fp8`` / ``moe_group_down_fp8``, ``moe_fp8``); the dense
+GEMMs stay bf16.
 """
 
 from __future__ import annotations
@@ -115,11 +118,22 @@ class GroupDecodeEngine:
         # fp8 grouped GEMMs measured SLOWER than bf16 hipBLASLt on ROCm 7
         # (skinny-M _scaled_mm + dynamic-quant overhead): keep groups bf16.
         # fp8 weights remain available for B=1 decode (DecodeEngine).
-        if os.environ.get("MDI_WEIGHT_DTYPE", "bf16") == "fp8":
+        # That verdict is about the library GEMMs: the MoE expert GEMMs
+        # are hand-written weight-bound kernels and do take fp8 slabs.
+        want_fp8 = os.environ.get("MDI_WEIGHT_DTYPE", "bf16") == "fp8"
+        self.moe_fp8 = (want_fp8 and self.moe
+                        and next(stage.parameters()).device.type == "cuda")
+        if want_fp8:
             import warnings
 
-            warnings.warn("grouped decode ignores MDI_WEIGHT_DTYPE=fp8 "
-                          "(bf16 is faster for batched GEMMs; see ROADMAP)")
+            if self.moe_fp8:
+                warnings.warn("grouped MoE decode: MDI_WEIGHT_DTYPE=fp8 "
+                              "applies to the expert GEMMs; only the dense "
+                              "GEMMs (qkv, proj, lm_head) stay bf16")
+            else:
+                warnings.warn("grouped decode ignores MDI_WEIGHT_DTYPE=fp8 "
+                              "(bf16 is faster for batched GEMMs; see "
+                              "ROADMAP)")
         # int4 weights exist only as B=1 decode GEMVs (DecodeEngine)
         if os.environ.get("MDI_WEIGHT_DTYPE", "bf16") == "int4":
             import warnings
@@ -145,6 +159,9 @@ class GroupDecodeEngine:
 
             for w in self.blocks:
                 w.quantize_fp8(cfg)
+        if self.moe_fp8:
+            for w in self.blocks:
+                w.quantize_fp8_experts()
         if self.is_starter:
             self.wte = stage.transformer.wte.weight.detach().contiguous()
             self.lnf_w = stage.transformer.ln_f.weight.detach().contiguous()
@@ -359,11 +376,20 @@ class GroupDecodeEngine:
         ops.moe_route_group(self.moe_eidx, self.moe_escale, self.moe_count,
                             self.moe_offset, self.moe_perm, self.moe_inv,
                             logits, k)
-        ops.moe_group_swiglu(self.ACT, w.fc1_w, w.fc2_w, hn, self.moe_count,
-                             self.moe_offset, self.moe_perm, self.moe_escale,
-                             k)
-        ops.moe_group_down(self.D, w.mlp_proj_w, self.ACT, self.moe_count,
-                           self.moe_offset, self.B)
+        if self.moe_fp8:
+            ops.moe_group_swiglu_fp8(self.ACT, w.fc1_w8, w.fc1_s, w.fc2_w8,
+                                     w.fc2_s, hn, self.moe_count,
+                                     self.moe_offset, self.moe_perm,
+                                     self.moe_escale, k)
+            ops.moe_group_down_fp8(self.D, w.mlp_proj_w8, w.mlp_proj_s,
+                                   self.ACT, self.moe_count, self.moe_offset,
+                                   self.B)
+        else:
+            ops.moe_group_swiglu(self.ACT, w.fc1_w, w.fc2_w, hn,
+                                 self.moe_count, self.moe_offset,
+                                 self.moe_perm, self.moe_escale, k)
+            ops.moe_group_down(self.D, w.mlp_proj_w, self.ACT,
+                               self.moe_count, self.moe_offset, self.B)
         # a is never self.X (it is the proj GEMM's output), so the
         # residual stream can land in place
         ops.moe_group_combine(self.X, a, self.D, self.moe_inv, k)

@@ -80,6 +80,25 @@ inline void check_fp8_weight(const torch::Tensor& W, int64_t M, int64_t K,
   TORCH_CHECK(W.numel() == M * K, name, " shape mismatch");
 }
 
+// Expert indirection of the fp8 GEMVs: W holds n stacked [M, K] slabs and
+// its scales n * M entries.  Returns n (0 without eidx: plain [M, K]).
+inline int64_t check_fp8_stack(const c10::optional<torch::Tensor>& eidx,
+                               const torch::Tensor& W, int64_t M, int64_t K,
+                               int64_t norm_kind, const char* name) {
+  if (!eidx.has_value()) {
+    check_fp8_weight(W, M, K, name);
+    return 0;
+  }
+  check_i32(*eidx, "eidx");
+  TORCH_CHECK(eidx->numel() > 0, "eidx is empty");
+  TORCH_CHECK(norm_kind != 2, "expert indirection: no LayerNorm");
+  TORCH_CHECK(W.is_cuda() && W.element_size() == 1 && W.is_contiguous(),
+              name, " must be contiguous fp8/uint8 on GPU");
+  TORCH_CHECK(W.numel() > 0 && W.numel() % (M * K) == 0, name,
+              ": stacked weight shape");
+  return W.numel() / (M * K);
+}
+
 void rmsnorm(torch::Tensor out, torch::Tensor x, torch::Tensor w,
              double eps) {
   check_bf16(out, "out");
@@ -148,16 +167,19 @@ void gemv_fp8(torch::Tensor out, torch::Tensor W, torch::Tensor wscale,
               c10::optional<torch::Tensor> res, int64_t epilogue,
               c10::optional<torch::Tensor> norm_w,
               c10::optional<torch::Tensor> norm_b, int64_t norm_kind,
-              double eps, int64_t rows) {
+              double eps, int64_t rows, c10::optional<torch::Tensor> eidx,
+              int64_t estride) {
   check_bf16(out, "out");
   check_bf16(x, "x");
   check_f32(wscale, "wscale");
   const int K = (int)x.numel();
   const int M = (int)out.numel();
   check_gemv_dims(M, K, epilogue, norm_kind);
-  check_fp8_weight(W, M, K, "W");
+  const int64_t n_slab = check_fp8_stack(eidx, W, M, K, norm_kind, "W");
   TORCH_CHECK(K % 16 == 0, "K must be a multiple of 16 for fp8 weights");
-  TORCH_CHECK(wscale.numel() == M, "wscale size");
+  TORCH_CHECK(wscale.numel() == (n_slab ? n_slab : 1) * M, "wscale size");
+  TORCH_CHECK(n_slab == 0 || estride == (int64_t)M * K,
+              "estride must be M * K");
   check_staged_lds(K);
   const void* bp = opt_bf16_vec(bias, M, "bias");
   const void* rp = opt_bf16_vec(res, M, "res");
@@ -166,7 +188,9 @@ void gemv_fp8(torch::Tensor out, torch::Tensor W, torch::Tensor wscale,
   const void* nbp = np.b;
   launch_gemv_fp8(out.data_ptr(), W.data_ptr(), wscale.data_ptr<float>(),
                   x.data_ptr(), bp, rp, nwp, nbp, (float)eps, M, K,
-                  (int)epilogue, (int)norm_kind, (int)rows, cur_stream());
+                  (int)epilogue, (int)norm_kind, (int)rows,
+                  n_slab ? eidx->data_ptr<int>() : nullptr,
+                  (long long)estride, (int)n_slab, cur_stream());
 }
 
 void gemv_swiglu_fp8(torch::Tensor out, torch::Tensor Wg,
@@ -174,7 +198,8 @@ void gemv_swiglu_fp8(torch::Tensor out, torch::Tensor Wg,
                      torch::Tensor uscale, torch::Tensor x, bool gelu_gate,
                      c10::optional<torch::Tensor> norm_w,
                      c10::optional<torch::Tensor> norm_b, int64_t norm_kind,
-                     double eps) {
+                     double eps, c10::optional<torch::Tensor> eidx,
+                     int64_t estride, c10::optional<torch::Tensor> escale) {
   check_bf16(out, "out");
   check_bf16(x, "x");
   check_f32(gscale, "gscale");
@@ -182,11 +207,21 @@ void gemv_swiglu_fp8(torch::Tensor out, torch::Tensor Wg,
   const int K = (int)x.numel();
   const int M = (int)out.numel();
   check_gemv_dims(M, K, 0, norm_kind);
-  check_fp8_weight(Wg, M, K, "Wg");
-  check_fp8_weight(Wu, M, K, "Wu");
+  const int64_t n_slab = check_fp8_stack(eidx, Wg, M, K, norm_kind, "Wg");
+  TORCH_CHECK(check_fp8_stack(eidx, Wu, M, K, norm_kind, "Wu") == n_slab,
+              "Wu: stacked weight shape");
   TORCH_CHECK(K % 16 == 0, "K must be a multiple of 16 for fp8 weights");
-  TORCH_CHECK(gscale.numel() == M && uscale.numel() == M,
+  const int64_t n_scale = (n_slab ? n_slab : 1) * M;
+  TORCH_CHECK(gscale.numel() == n_scale && uscale.numel() == n_scale,
               "gscale/uscale size");
+  TORCH_CHECK(n_slab == 0 || estride == (int64_t)M * K,
+              "estride must be M * K");
+  const float* esp = nullptr;
+  if (escale.has_value()) {
+    check_f32(*escale, "escale");
+    TORCH_CHECK(escale->numel() > 0, "escale is empty");
+    esp = escale->data_ptr<float>();
+  }
   check_staged_lds(K);
   const NormPtrs np = check_norm(norm_w, norm_b, norm_kind, K);
   const void* nwp = np.w;
@@ -195,7 +230,9 @@ void gemv_swiglu_fp8(torch::Tensor out, torch::Tensor Wg,
                          gscale.data_ptr<float>(), Wu.data_ptr(),
                          uscale.data_ptr<float>(), x.data_ptr(), nwp, nbp,
                          (float)eps, M, K, gelu_gate ? 1 : 0,
-                         (int)norm_kind, cur_stream());
+                         (int)norm_kind,
+                         n_slab ? eidx->data_ptr<int>() : nullptr,
+                         (long long)estride, (int)n_slab, esp, cur_stream());
 }
 
 // packed int4 weights [M, Kp/2] (uint8) + bf16 (scale, zero) [M, Kp/128, 2]
@@ -437,6 +474,74 @@ void moe_group_down(torch::Tensor D, torch::Tensor Wd, torch::Tensor act,
       (int)n_tokens, (int)n_e, (int)M, (int)K, (int)(R / n_tokens), 0,
       cur_stream());
   TORCH_CHECK(rc == 0, "moe_group_down: needs K % 32 == 0, M % 16 == 0, "
+                       "B <= 128, n_e <= 64, k <= 8");
+}
+
+// fp8 slab [n_e, M, K] + fp32 row scales [n_e, M]
+inline void check_fp8_slab(const torch::Tensor& W, const torch::Tensor& s,
+                           const char* name) {
+  TORCH_CHECK(W.is_cuda() && W.element_size() == 1 && W.is_contiguous() &&
+                  W.dim() == 3,
+              name, " must be a contiguous fp8/uint8 [n_e, M, K] on GPU");
+  check_f32(s, name);
+  TORCH_CHECK(s.numel() == W.size(0) * W.size(1), name,
+              ": scales must be [n_e, M]");
+}
+
+void moe_group_swiglu_fp8(torch::Tensor act, torch::Tensor Wg,
+                          torch::Tensor gscale, torch::Tensor Wu,
+                          torch::Tensor uscale, torch::Tensor X,
+                          torch::Tensor count, torch::Tensor offset,
+                          torch::Tensor perm, torch::Tensor escale,
+                          int64_t k) {
+  check_bf16(act, "act");
+  check_fp8_slab(Wg, gscale, "Wg");
+  check_fp8_slab(Wu, uscale, "Wu");
+  check_bf16(X, "X");
+  TORCH_CHECK(X.dim() == 2 && act.dim() == 2,
+              "moe_group_swiglu_fp8: X [B,K], act [B*k,M]");
+  const int64_t n_e = Wg.size(0), M = Wg.size(1), K = Wg.size(2);
+  const int64_t B = X.size(0);
+  TORCH_CHECK(Wu.sizes() == Wg.sizes(), "Wu shape");
+  TORCH_CHECK(X.size(1) == K && act.size(0) == B * k && act.size(1) == M,
+              "moe_group_swiglu_fp8: size mismatch");
+  check_i32n(count, "count", n_e);
+  check_i32n(offset, "offset", n_e + 1);
+  check_i32n(perm, "perm", B * k);
+  check_f32(escale, "escale");
+  TORCH_CHECK(escale.numel() == B * k, "escale size");
+  const int rc = launch_moe_group_gemm_fp8(
+      act.data_ptr(), Wg.data_ptr(), gscale.data_ptr<float>(), Wu.data_ptr(),
+      uscale.data_ptr<float>(), X.data_ptr(), count.data_ptr<int>(),
+      offset.data_ptr<int>(), perm.data_ptr<int>(), escale.data_ptr<float>(),
+      (int)B, (int)n_e, (int)M, (int)K, (int)k, 1, cur_stream());
+  TORCH_CHECK(rc == 0, "moe_group_swiglu_fp8: needs K % 32 == 0, "
+                       "M % 16 == 0, B <= 128, n_e <= 64, k <= 8");
+}
+
+void moe_group_down_fp8(torch::Tensor D, torch::Tensor Wd,
+                        torch::Tensor dscale, torch::Tensor act,
+                        torch::Tensor count, torch::Tensor offset,
+                        int64_t n_tokens) {
+  check_f32(D, "D");
+  check_fp8_slab(Wd, dscale, "Wd");
+  check_bf16(act, "act");
+  TORCH_CHECK(act.dim() == 2 && D.dim() == 2,
+              "moe_group_down_fp8: act [B*k,K], D [B*k,M]");
+  const int64_t n_e = Wd.size(0), M = Wd.size(1), K = Wd.size(2);
+  const int64_t R = act.size(0);
+  TORCH_CHECK(n_tokens >= 1 && R % n_tokens == 0,
+              "moe_group_down_fp8: rows must be n_tokens * k");
+  TORCH_CHECK(act.size(1) == K && D.size(0) == R && D.size(1) == M,
+              "moe_group_down_fp8: size mismatch");
+  check_i32n(count, "count", n_e);
+  check_i32n(offset, "offset", n_e + 1);
+  const int rc = launch_moe_group_gemm_fp8(
+      D.data_ptr(), Wd.data_ptr(), dscale.data_ptr<float>(), nullptr,
+      nullptr, act.data_ptr(), count.data_ptr<int>(),
+      offset.data_ptr<int>(), nullptr, nullptr, (int)n_tokens, (int)n_e,
+      (int)M, (int)K, (int)(R / n_tokens), 0, cur_stream());
+  TORCH_CHECK(rc == 0, "moe_group_down_fp8: needs K % 32 == 0, M % 16 == 0, "
                        "B <= 128, n_e <= 64, k <= 8");
 }
 
@@ -806,13 +911,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("bias"), py::arg("res"), py::arg("epilogue"),
         py::arg("norm_w") = c10::nullopt, py::arg("norm_b") = c10::nullopt,
         py::arg("norm_kind") = 0, py::arg("eps") = 1e-5,
-        py::arg("rows") = 0);
+        py::arg("rows") = 0, py::arg("eidx") = c10::nullopt,
+        py::arg("estride") = 0);
   m.def("gemv_swiglu_fp8", &gemv_swiglu_fp8,
         "fused SwiGLU pair GEMV with fp8 weights",
         py::arg("out"), py::arg("Wg"), py::arg("gscale"), py::arg("Wu"),
         py::arg("uscale"), py::arg("x"), py::arg("gelu_gate"),
         py::arg("norm_w") = c10::nullopt, py::arg("norm_b") = c10::nullopt,
-        py::arg("norm_kind") = 0, py::arg("eps") = 1e-5);
+        py::arg("norm_kind") = 0, py::arg("eps") = 1e-5,
+        py::arg("eidx") = c10::nullopt, py::arg("estride") = 0,
+        py::arg("escale") = c10::nullopt);
   m.def("gemv_int4", &gemv_int4,
         "decode GEMV with int4 group-quantized weights (128-group bf16 "
         "scale/zero)",
@@ -855,6 +963,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "grouped MoE down MFMA GEMM over the permuted rows (fp32 out)",
         py::arg("D"), py::arg("Wd"), py::arg("act"), py::arg("count"),
         py::arg("offset"), py::arg("n_tokens"));
+  m.def("moe_group_swiglu_fp8", &moe_group_swiglu_fp8,
+        "moe_group_swiglu with fp8(e4m3) slabs + fp32 row scales [n_e, M]",
+        py::arg("act"), py::arg("Wg"), py::arg("gscale"), py::arg("Wu"),
+        py::arg("uscale"), py::arg("X"), py::arg("count"),
+        py::arg("offset"), py::arg("perm"), py::arg("escale"), py::arg("k"));
+  m.def("moe_group_down_fp8", &moe_group_down_fp8,
+        "moe_group_down with an fp8(e4m3) slab + fp32 row scales [n_e, M]",
+        py::arg("D"), py::arg("Wd"), py::arg("dscale"), py::arg("act"),
+        py::arg("count"), py::arg("offset"), py::arg("n_tokens"));
   m.def("moe_group_combine", &moe_group_combine,
         "out[b] = res[b] + sum over ranks of the token's expert rows",
         py::arg("out"), py::arg("res"), py::arg("D"), py::arg("inv"),

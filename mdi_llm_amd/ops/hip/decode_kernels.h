@@ -24,19 +24,23 @@ void launch_gemv(void* out, const void* W, const void* x, const void* bias,
                  int rows, const int* eidx, long long estride,
                  hipStream_t stream);
 
-// fp8(e4m3)-weight variants: W is bytes, wscale fp32 per output row
+// fp8(e4m3)-weight variants: W is bytes, wscale fp32 per output row.
+// eidx (device int, or nullptr) picks one of n_slab stacked [M, K] slabs
+// estride bytes apart and its M scales at replay time.
 void launch_gemv_fp8(void* out, const void* W, const float* wscale,
                      const void* x, const void* bias, const void* res,
                      const void* norm_w, const void* norm_b, float eps,
                      int M, int K, int epilogue, int norm_kind, int rows,
+                     const int* eidx, long long estride, int n_slab,
                      hipStream_t stream);
 
 void launch_gemv_swiglu_fp8(void* out, const void* Wg, const float* gscale,
                             const void* Wu, const float* uscale,
                             const void* x, const void* norm_w,
                             const void* norm_b, float eps, int M, int K,
-                            int gelu_gate, int norm_kind,
-                            hipStream_t stream);
+                            int gelu_gate, int norm_kind, const int* eidx,
+                            long long estride, int n_slab,
+                            const float* escale, hipStream_t stream);
 
 // int4 group-quantized variants: W is [M, Kp/2] packed nibbles with
 // Kp = ceil(K/128)*128, qparams bf16 [M, Kp/128, 2] = (scale, zero) per
@@ -86,6 +90,15 @@ int launch_moe_group_gemm(void* out, const void* Wa, const void* Wb,
                           const int* perm, const float* escale, int Bsz,
                           int n_e, int M, int K, int k_top, int swiglu,
                           hipStream_t stream);
+
+// the same with fp8(e4m3) slabs [n_e, M, K] and fp32 row scales [n_e, M]
+// (sa for Wa, sb for Wb); activations and the MFMA stay bf16
+int launch_moe_group_gemm_fp8(void* out, const void* Wa, const float* sa,
+                              const void* Wb, const float* sb, const void* X,
+                              const int* count, const int* offset,
+                              const int* perm, const float* escale, int Bsz,
+                              int n_e, int M, int K, int k_top, int swiglu,
+                              hipStream_t stream);
 
 // out[b] = res[b] + sum_rank D[inv[b*k + rank]] (fp32, rank order)
 void launch_moe_group_combine(void* out, const void* res, const float* D,

@@ -56,6 +56,12 @@ DEVINL i32x4_t load16_nt_u8(const unsigned char* p) {
   return __builtin_nontemporal_load(reinterpret_cast<const i32x4_t*>(p));
 }
 
+using i32x2_t = __attribute__((ext_vector_type(2))) int;
+
+DEVINL i32x2_t load8_nt_u8(const unsigned char* p) {
+  return __builtin_nontemporal_load(reinterpret_cast<const i32x2_t*>(p));
+}
+
 using f32x4 = __attribute__((__vector_size__(16))) float;
 using bf16x8_t = __attribute__((ext_vector_type(8))) __bf16;
 
@@ -100,6 +106,23 @@ DEVINL bf16x8_t fp8x8_to_bf16(const u8kv* p, float scl) {
   r[6] = (__bf16)(d.x * scl);
   r[7] = (__bf16)(d.y * scl);
   return r;
+}
+
+// 8 fp8 bytes (k ascending: lo then hi) -> 8 bf16, unscaled.  e4m3 has 3
+// mantissa bits, so the fp32 convert is exact and its low 16 bits are
+// zero: keeping the high halves IS the bf16 value (no rounding step).
+DEVINL unsigned bf16_pair_hi(float a, float b) {
+  return (__float_as_uint(a) >> 16) | (__float_as_uint(b) & 0xffff0000u);
+}
+
+DEVINL bf16x8_t fp8x8_to_bf16_exact(int lo, int hi) {
+  const v2fkv a = __builtin_amdgcn_cvt_pk_f32_fp8(lo, false);
+  const v2fkv b = __builtin_amdgcn_cvt_pk_f32_fp8(lo, true);
+  const v2fkv c = __builtin_amdgcn_cvt_pk_f32_fp8(hi, false);
+  const v2fkv d = __builtin_amdgcn_cvt_pk_f32_fp8(hi, true);
+  unsigned w[4] = {bf16_pair_hi(a.x, a.y), bf16_pair_hi(b.x, b.y),
+                   bf16_pair_hi(c.x, c.y), bf16_pair_hi(d.x, d.y)};
+  return *reinterpret_cast<const bf16x8_t*>(w);
 }
 
 // PV accumulate straight from the fp8 pairs (skips the bf16 round trip
@@ -905,11 +928,24 @@ __global__ __launch_bounds__(1024) void moe_route_group_kernel(
 // K-reduce scratch ([2][4 waves][RB][16] fp32 <= 64 KB) overlays the X
 // buffers once the last chunk is consumed.
 // K % 32 == 0 (a wave skips the 32-wide steps past K), M % 16 == 0.
-template <int RB, bool SWIGLU>
+//
+// W8: the slabs are fp8 e4m3 bytes with one fp32 scale per output row
+// (sa/sb [n_e, M]).  The bytes are converted to bf16 in registers (exact)
+// and feed the same bf16 MFMA; the row scale multiplies the reduced fp32
+// sum once in the epilogue (the gate's before its silu).  A lane's natural
+// fragment would be 8 B, so where a wave owns >= 64 k per chunk a lane
+// loads 16 B = 16 consecutive k and feeds TWO MFMAs: the contraction order
+// is free as long as A and B agree, so MFMA h of a 64-wide step contracts
+// k = sub*16 + h*8 + (0..7) and reads its X fragment at that offset (64 B
+// per row per step, as the bf16 kernel).  RB=128 (32 k per wave per chunk)
+// keeps 8-B loads.
+template <int RB, bool SWIGLU, bool W8>
 __global__ __launch_bounds__(256) void moe_group_gemm_kernel(
     void* __restrict__ outp,            // SWIGLU: bf16 [nrows, M]; else fp32
-    const bf16* __restrict__ Wa,        // [n_e, M, K] gate (or down) slabs
-    const bf16* __restrict__ Wb,        // [n_e, M, K] up slabs (SWIGLU)
+    const void* __restrict__ Wav,       // [n_e, M, K] gate (or down) slabs
+    const void* __restrict__ Wbv,       // [n_e, M, K] up slabs (SWIGLU)
+    const float* __restrict__ sa,       // W8: [n_e, M] row scales of Wa
+    const float* __restrict__ sb,       // W8 && SWIGLU: of Wb
     const bf16* __restrict__ X,         // SWIGLU: [B, K] tokens; else
                                         // [nrows, K] permuted activations
     const int* __restrict__ count, const int* __restrict__ offset,
@@ -918,7 +954,11 @@ __global__ __launch_bounds__(256) void moe_group_gemm_kernel(
   constexpr int KC = (RB <= 32) ? 512 : (RB <= 64 ? 256 : 128);
   constexpr int BT = RB / 16;
   constexpr int PRE = RB * KC / 8 / 256;
-  constexpr int SPC = KC / 4 / 32;
+  constexpr int STEP = (W8 && KC / 4 >= 64) ? 64 : 32;  // k per ring slot
+  constexpr int SPC = KC / 4 / STEP;
+  // one ring slot: 8 bf16, or STEP/4 fp8 bytes in the low STEP/16 words
+  using wreg = typename std::conditional<W8, i32x4_t, bf16x8>::type;
+  using welt = typename std::conditional<W8, unsigned char, bf16>::type;
   const int e = blockIdx.y;
   const int cnt = min(count[e], RB);
   const int off = offset[e];
@@ -937,7 +977,7 @@ __global__ __launch_bounds__(256) void moe_group_gemm_kernel(
   const int row0 = (int)blockIdx.x * 16;
   const int arow = lane & 15;
   const int sub = lane >> 4;
-  const int koff = sub * 8;
+  const int koff = sub * (STEP / 4);
   const int nt = (cnt + 15) >> 4;       // token tiles in use
   const int rows_used = nt * 16;
   const int nch = (K + KC - 1) / KC;
@@ -996,25 +1036,47 @@ __global__ __launch_bounds__(256) void moe_group_gemm_kernel(
   };
 
   const size_t wofs = ((size_t)e * M + row0 + arow) * (size_t)K;
-  const bf16* wa = Wa + wofs;
-  const bf16* wb = SWIGLU ? Wb + wofs : nullptr;
+  const welt* wa = static_cast<const welt*>(Wav) + wofs;
+  const welt* wb = SWIGLU ? static_cast<const welt*>(Wbv) + wofs : nullptr;
   const int q0 = wave * (KC / 4);
-  auto wload = [&](int ci, bf16x8 (&ra)[SPC], bf16x8 (&rb)[SPC]) {
+  auto wload = [&](int ci, wreg (&ra)[SPC], wreg (&rb)[SPC]) {
 #pragma unroll
     for (int s = 0; s < SPC; ++s) {
-      const int kk = ci * KC + q0 + s * 32;
-      if (kk < K) {
-        ra[s] = load8_nt(wa + kk + koff);
-        if (SWIGLU) rb[s] = load8_nt(wb + kk + koff);
+      const int kk = ci * KC + q0 + s * STEP;
+      if constexpr (W8) {
+        // K % 32 == 0: the last 64-wide step may hold only 32 k, so the
+        // bound is per lane, and a lane past K holds zeros (its X is
+        // staged as zeros; stale bytes could decode to NaN)
+        const bool ok = kk + koff < K;
+        if constexpr (STEP == 64) {
+          const i32x4_t z = {0, 0, 0, 0};
+          ra[s] = ok ? load16_nt_u8(wa + kk + koff) : z;
+          if (SWIGLU) rb[s] = ok ? load16_nt_u8(wb + kk + koff) : z;
+        } else {
+          const i32x2_t z = {0, 0};
+          const i32x2_t va = ok ? load8_nt_u8(wa + kk + koff) : z;
+          ra[s][0] = va[0];
+          ra[s][1] = va[1];
+          if (SWIGLU) {
+            const i32x2_t vb = ok ? load8_nt_u8(wb + kk + koff) : z;
+            rb[s][0] = vb[0];
+            rb[s][1] = vb[1];
+          }
+        }
+      } else {
+        if (kk < K) {
+          ra[s] = load8_nt(wa + kk + koff);
+          if (SWIGLU) rb[s] = load8_nt(wb + kk + koff);
+        }
       }
     }
   };
 
   // W rings first (the loads fly across the X staging), then X chunk 0
-  bf16x8 wra[2][SPC], wrb[2][SPC];
+  wreg wra[2][SPC], wrb[2][SPC];
 #pragma unroll
   for (int s = 0; s < SPC; ++s) {
-    *reinterpret_cast<int4*>(wra[0][s].v) = make_int4(0, 0, 0, 0);
+    *reinterpret_cast<int4*>(&wra[0][s]) = make_int4(0, 0, 0, 0);
     wra[1][s] = wra[0][s];
     wrb[0][s] = wra[0][s];
     wrb[1][s] = wra[0][s];
@@ -1030,27 +1092,36 @@ __global__ __launch_bounds__(256) void moe_group_gemm_kernel(
 
   // ring slot and LDS buffer are compile-time per call (see
   // mtile_gemm_kernel: a runtime-indexed ring spills to scratch)
-  auto chunk_body = [&](int ci, bf16x8 (&ra)[SPC], bf16x8 (&rb)[SPC],
+  auto chunk_body = [&](int ci, wreg (&ra)[SPC], wreg (&rb)[SPC],
                         bf16* cur, bf16* nxt) {
     bf16x8 pre[PRE];
     const bool more = ci + 1 < nch;
     if (more) xload((ci + 1) * KC, pre);
 #pragma unroll
     for (int s = 0; s < SPC; ++s) {
-      const int kl = q0 + s * 32;
+      const int kl = q0 + s * STEP;
       if (ci * KC + kl < K) {
-        const bf16x8_t wfa = *reinterpret_cast<const bf16x8_t*>(ra[s].v);
-        const bf16x8_t wfb = *reinterpret_cast<const bf16x8_t*>(rb[s].v);
 #pragma unroll
-        for (int t = 0; t < BT; ++t) {
-          if (t < nt) {
-            const bf16x8_t xf = *reinterpret_cast<const bf16x8_t*>(
-                &cur[x_swz<KC>(t * 16 + arow, kl + koff)]);
-            acca[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                wfa, xf, acca[t], 0, 0, 0);
-            if (SWIGLU)
-              accb[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                  wfb, xf, accb[t], 0, 0, 0);
+        for (int h = 0; h < STEP / 32; ++h) {
+          bf16x8_t wfa, wfb;
+          if constexpr (W8) {
+            wfa = fp8x8_to_bf16_exact(ra[s][2 * h], ra[s][2 * h + 1]);
+            wfb = fp8x8_to_bf16_exact(rb[s][2 * h], rb[s][2 * h + 1]);
+          } else {
+            wfa = *reinterpret_cast<const bf16x8_t*>(&ra[s]);
+            wfb = *reinterpret_cast<const bf16x8_t*>(&rb[s]);
+          }
+#pragma unroll
+          for (int t = 0; t < BT; ++t) {
+            if (t < nt) {
+              const bf16x8_t xf = *reinterpret_cast<const bf16x8_t*>(
+                  &cur[x_swz<KC>(t * 16 + arow, kl + koff + h * 8)]);
+              acca[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                  wfa, xf, acca[t], 0, 0, 0);
+              if (SWIGLU)
+                accb[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                    wfb, xf, accb[t], 0, 0, 0);
+            }
           }
         }
       }
@@ -1089,13 +1160,16 @@ __global__ __launch_bounds__(256) void moe_group_gemm_kernel(
     const int s = off + c;
     if (s >= nrows) continue;
     const int idx = c * 16 + ((r + c) & 15);
-    const float a = c_red[idx] + c_red[CW + idx] + c_red[2 * CW + idx] +
-                    c_red[3 * CW + idx];
+    float a = c_red[idx] + c_red[CW + idx] + c_red[2 * CW + idx] +
+              c_red[3 * CW + idx];
+    const size_t so = (size_t)e * M + row0 + r;  // W8: this row's scale
+    if constexpr (W8) a *= sa[so];
     const size_t o = (size_t)s * M + row0 + r;
     if (SWIGLU) {
       const float* cu = c_red + 4 * CW;
-      const float u = cu[idx] + cu[CW + idx] + cu[2 * CW + idx] +
-                      cu[3 * CW + idx];
+      float u = cu[idx] + cu[CW + idx] + cu[2 * CW + idx] +
+                cu[3 * CW + idx];
+      if constexpr (W8) u *= sb[so];
       const float act = a / (1.f + expf(-a));
       // routing weight in fp32 before the bf16 rounding (as gemv_swiglu)
       reinterpret_cast<bf16*>(outp)[o] = f2b(act * u * sscale[c]);
@@ -1162,6 +1236,9 @@ DEVINL float dot16_fp8(const unsigned* wq, const bf16* xs) {
   return acc;
 }
 
+// eidx/estride select an expert slab from stacked [n_slab, M, K] bytes and
+// its [n_slab, M] scales at launch-replay time (as gemv_direct_kernel); the
+// device-side index is clamped to the slabs that exist.
 template <int EPI, int NORM, int ROWS>
 __global__ void gemv_fp8_kernel(bf16* __restrict__ out,
                                 const unsigned char* __restrict__ W,
@@ -1171,10 +1248,17 @@ __global__ void gemv_fp8_kernel(bf16* __restrict__ out,
                                 const bf16* __restrict__ res,
                                 const bf16* __restrict__ nw,
                                 const bf16* __restrict__ nb, float eps,
-                                int M, int K) {
+                                int M, int K,
+                                const int* __restrict__ eidx,
+                                long long estride, int n_slab) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __shared__ float red[8];
   bf16* xs = reinterpret_cast<bf16*>(smem);
+  if (eidx != nullptr) {
+    const int e = min(max(eidx[0], 0), n_slab - 1);
+    W += (size_t)e * (size_t)estride;
+    wscale += (size_t)e * M;
+  }
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -1240,10 +1324,20 @@ __global__ void gemv_swiglu_fp8_kernel(
     const float* __restrict__ gscale, const unsigned char* __restrict__ Wu,
     const float* __restrict__ uscale, const bf16* __restrict__ x,
     const bf16* __restrict__ nw, const bf16* __restrict__ nb, float eps,
-    int M, int K, int gelu_gate) {
+    int M, int K, int gelu_gate, const int* __restrict__ eidx,
+    long long estride, int n_slab, const float* __restrict__ escale) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __shared__ float red[8];
   bf16* xs = reinterpret_cast<bf16*>(smem);
+  if (eidx != nullptr) {  // expert slab + its row scales (see gemv_fp8)
+    const int e = min(max(eidx[0], 0), n_slab - 1);
+    const size_t off = (size_t)e * (size_t)estride;
+    Wg += off;
+    Wu += off;
+    gscale += (size_t)e * M;
+    uscale += (size_t)e * M;
+  }
+  const float oscale = (escale != nullptr) ? escale[0] : 1.f;
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -1269,7 +1363,8 @@ __global__ void gemv_swiglu_fp8_kernel(
       ga *= gscale[row];
       ua *= uscale[row];
       float act = gelu_gate ? gelu_tanh(ga) : ga / (1.f + expf(-ga));
-      out[row] = f2b(act * ua);
+      // routing weight in fp32 before the bf16 rounding (as gemv_swiglu)
+      out[row] = f2b(act * ua * oscale);
     }
   }
 }
@@ -3865,6 +3960,7 @@ void launch_gemv_fp8(void* out, const void* W, const float* wscale,
                      const void* x, const void* bias, const void* res,
                      const void* norm_w, const void* norm_b, float eps,
                      int M, int K, int epilogue, int norm_kind, int rows,
+                     const int* eidx, long long estride, int n_slab,
                      hipStream_t stream) {
   const int smem = K * sizeof(bf16);
   if (rows == 0) rows = M >= 32768 ? 4 : (M > 8192 ? 2 : 1);
@@ -3873,7 +3969,8 @@ void launch_gemv_fp8(void* out, const void* W, const float* wscale,
   hipLaunchKernelGGL((gemv_fp8_kernel<E, N, R>), grid, block, smem, stream, \
                      (bf16*)out, (const unsigned char*)W, wscale,           \
                      (const bf16*)x, (const bf16*)bias, (const bf16*)res,   \
-                     (const bf16*)norm_w, (const bf16*)norm_b, eps, M, K)
+                     (const bf16*)norm_w, (const bf16*)norm_b, eps, M, K,   \
+                     eidx, estride, n_slab)
 #define GEMV8_CASE(E, N)                                                    \
   do {                                                                      \
     if (rows == 4) GEMV8_CASE1(E, N, 4);                                    \
@@ -3903,8 +4000,9 @@ void launch_gemv_swiglu_fp8(void* out, const void* Wg, const float* gscale,
                             const void* Wu, const float* uscale,
                             const void* x, const void* norm_w,
                             const void* norm_b, float eps, int M, int K,
-                            int gelu_gate, int norm_kind,
-                            hipStream_t stream) {
+                            int gelu_gate, int norm_kind, const int* eidx,
+                            long long estride, int n_slab,
+                            const float* escale, hipStream_t stream) {
   const int smem = K * sizeof(bf16);
   dim3 grid(gemv_grid(M, 4)), block(256);
 #define SW8_CASE(N)                                                         \
@@ -3912,7 +4010,7 @@ void launch_gemv_swiglu_fp8(void* out, const void* Wg, const float* gscale,
                      stream, (bf16*)out, (const unsigned char*)Wg, gscale,  \
                      (const unsigned char*)Wu, uscale, (const bf16*)x,      \
                      (const bf16*)norm_w, (const bf16*)norm_b, eps, M, K,   \
-                     gelu_gate)
+                     gelu_gate, eidx, estride, n_slab, escale)
   switch (norm_kind) {
     case 1: SW8_CASE(1); break;
     case 2: SW8_CASE(2); break;
@@ -4037,11 +4135,14 @@ void launch_moe_route_group(int* eidx, float* escale, int* count,
 // swiglu != 0: out = bf16 ACT[B*k, M] from tokens X[B, K];
 // swiglu == 0: out = fp32 D[B*k, M] from permuted rows X[B*k, K].
 // Returns -1 when the shape has no instantiation.
-int launch_moe_group_gemm(void* out, const void* Wa, const void* Wb,
-                          const void* X, const int* count, const int* offset,
-                          const int* perm, const float* escale, int Bsz,
-                          int n_e, int M, int K, int k_top, int swiglu,
-                          hipStream_t stream) {
+template <bool W8>
+static int moe_group_gemm_dispatch(void* out, const void* Wa, const void* Wb,
+                                   const float* sa, const float* sb,
+                                   const void* X, const int* count,
+                                   const int* offset, const int* perm,
+                                   const float* escale, int Bsz, int n_e,
+                                   int M, int K, int k_top, int swiglu,
+                                   hipStream_t stream) {
   if (M % 16 != 0 || K % 32 != 0 || Bsz < 1 || Bsz > MOE_MAX_B ||
       n_e < 1 || n_e > MOE_MAX_E || k_top < 1 || k_top > MOE_MAX_TOPK)
     return -1;
@@ -4052,14 +4153,15 @@ int launch_moe_group_gemm(void* out, const void* Wa, const void* Wb,
     static bool attr_set = false;                                           \
     if (!attr_set) {                                                        \
       (void)hipFuncSetAttribute(                                            \
-          reinterpret_cast<const void*>(&moe_group_gemm_kernel<RBB, SW>),   \
+          reinterpret_cast<const void*>(                                    \
+              &moe_group_gemm_kernel<RBB, SW, W8>),                         \
           hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);           \
       attr_set = true;                                                      \
     }                                                                       \
-    hipLaunchKernelGGL((moe_group_gemm_kernel<RBB, SW>), grid, dim3(256),   \
-                       (size_t)2 * RBB * KCC * 2, stream, out,              \
-                       (const bf16*)Wa, (const bf16*)Wb, (const bf16*)X,    \
-                       count, offset, perm, escale, M, K, k_top, nrows);    \
+    hipLaunchKernelGGL((moe_group_gemm_kernel<RBB, SW, W8>), grid,          \
+                       dim3(256), (size_t)2 * RBB * KCC * 2, stream, out,   \
+                       Wa, Wb, sa, sb, (const bf16*)X, count, offset, perm, \
+                       escale, M, K, k_top, nrows);                         \
     return 0;                                                               \
   }
 #define MOE_CASE(RBB, KCC)                                                  \
@@ -4073,6 +4175,27 @@ int launch_moe_group_gemm(void* out, const void* Wa, const void* Wb,
 #undef MOE_CASE
 #undef MOE_CASE1
   return -1;
+}
+
+int launch_moe_group_gemm(void* out, const void* Wa, const void* Wb,
+                          const void* X, const int* count, const int* offset,
+                          const int* perm, const float* escale, int Bsz,
+                          int n_e, int M, int K, int k_top, int swiglu,
+                          hipStream_t stream) {
+  return moe_group_gemm_dispatch<false>(out, Wa, Wb, nullptr, nullptr, X,
+                                        count, offset, perm, escale, Bsz,
+                                        n_e, M, K, k_top, swiglu, stream);
+}
+
+int launch_moe_group_gemm_fp8(void* out, const void* Wa, const float* sa,
+                              const void* Wb, const float* sb, const void* X,
+                              const int* count, const int* offset,
+                              const int* perm, const float* escale, int Bsz,
+                              int n_e, int M, int K, int k_top, int swiglu,
+                              hipStream_t stream) {
+  return moe_group_gemm_dispatch<true>(out, Wa, Wb, sa, sb, X, count, offset,
+                                       perm, escale, Bsz, n_e, M, K, k_top,
+                                       swiglu, stream);
 }
 
 void launch_moe_group_combine(void* out, const void* res, const float* D,

@@ -99,6 +99,68 @@ inline int64_t check_fp8_stack(const c10::optional<torch::Tensor>& eidx,
   return W.numel() / (M * K);
 }
 
+// Geometry of one prefill call, checked in full before any launch: the
+// kernels index the pools with slot, layer and pos0 + t as given, so a
+// value out of range would read or write outside the cache.
+struct PrefillGeom {
+  int n_layers, n_kv, max_seq, hs, qpk, T;
+  bool kv8;
+};
+
+inline PrefillGeom check_prefill(const char* op, const torch::Tensor& qkv,
+                                 const torch::Tensor& kpool,
+                                 const torch::Tensor& vpool,
+                                 const c10::optional<torch::Tensor>& kscale,
+                                 const c10::optional<torch::Tensor>& vscale,
+                                 int64_t pos0, int64_t slot, int64_t layer) {
+  check_bf16(qkv, "qkv");
+  TORCH_CHECK(kscale.has_value() == vscale.has_value(), op,
+              ": kscale and vscale go together");
+  const bool kv8 = kscale.has_value();
+  if (kv8) {
+    TORCH_CHECK(kpool.scalar_type() == torch::kUInt8 &&
+                    vpool.scalar_type() == torch::kUInt8,
+                "fp8 KV cache must be uint8 pools");
+    TORCH_CHECK(kpool.is_cuda() && vpool.is_cuda() &&
+                    kpool.is_contiguous() && vpool.is_contiguous(),
+                op, ": pools must be contiguous on GPU");
+    check_f32(*kscale, "kscale");
+    check_f32(*vscale, "vscale");
+  } else {
+    check_bf16(kpool, "kpool");
+    check_bf16(vpool, "vpool");
+  }
+  // pool: [slots, layers, kv_heads, max_seq, head_size]
+  TORCH_CHECK(kpool.dim() == 5 && vpool.dim() == 5, op,
+              ": pools must be 5-D");
+  TORCH_CHECK(kpool.sizes() == vpool.sizes(), op,
+              ": kpool and vpool differ in shape");
+  if (kv8) {
+    const auto want = kpool.sizes().slice(0, 4);
+    TORCH_CHECK(kscale->sizes() == want && vscale->sizes() == want, op,
+                ": scales must be [slots, layers, n_kv, max_seq]");
+  }
+  const int64_t n_slots = kpool.size(0);
+  const int64_t n_layers = kpool.size(1);
+  const int64_t n_kv = kpool.size(2);
+  const int64_t max_seq = kpool.size(3);
+  const int64_t hs = kpool.size(4);
+  TORCH_CHECK(n_kv > 0 && hs > 0, op, ": empty pool");
+  TORCH_CHECK(qkv.dim() == 2, op, ": qkv must be [T, qkv_dim]");
+  const int64_t T = qkv.size(0);
+  TORCH_CHECK(T >= 1, op, ": T must be at least 1");
+  const int64_t qpk = qkv.size(1) / (n_kv * hs) - 2;
+  TORCH_CHECK(qpk >= 1 && qkv.size(1) == n_kv * (qpk + 2) * hs, op,
+              ": qkv width must be n_kv * (qpk + 2) * head_size, qpk >= 1");
+  TORCH_CHECK(pos0 >= 0 && pos0 + T <= max_seq, op,
+              ": pos0 + T overflows the pool (pos0=", pos0, " T=", T,
+              " max_seq=", max_seq, ")");
+  TORCH_CHECK(slot >= 0 && slot < n_slots, op, ": slot out of range");
+  TORCH_CHECK(layer >= 0 && layer < n_layers, op, ": layer out of range");
+  return PrefillGeom{(int)n_layers, (int)n_kv, (int)max_seq, (int)hs,
+                     (int)qpk, (int)T, kv8};
+}
+
 void rmsnorm(torch::Tensor out, torch::Tensor x, torch::Tensor w,
              double eps) {
   check_bf16(out, "out");
@@ -768,15 +830,23 @@ void mtile_gemm(torch::Tensor Y, torch::Tensor W, torch::Tensor X,
   check_bf16(Y, "Y");
   check_bf16(W, "W");
   check_bf16(X, "X");
+  TORCH_CHECK(W.dim() == 2 && X.dim() == 2,
+              "mtile_gemm: W and X must be 2-D");
   const int Bsz = (int)X.size(0);
   const int K = (int)X.size(1);
   const int M = (int)W.size(0);
   TORCH_CHECK((int)W.size(1) == K, "mtile_gemm: K mismatch");
   TORCH_CHECK(Y.numel() >= (int64_t)Bsz * M, "mtile_gemm: Y too small");
+  // the epilogue reads bias[m] and res[b * M + m] unconditionally
+  const void* bp = opt_bf16_vec(bias, M, "bias");
+  const void* rp = opt_bf16_vec(res, (int64_t)Bsz * M, "res");
+  const auto dev = Y.device();
+  TORCH_CHECK(W.device() == dev && X.device() == dev &&
+                  (!bias.has_value() || bias->device() == dev) &&
+                  (!res.has_value() || res->device() == dev),
+              "mtile_gemm: all tensors must be on one device");
   int rc = launch_mtile_gemm(
-      Y.data_ptr(), W.data_ptr(), X.data_ptr(),
-      bias.has_value() ? bias->data_ptr() : nullptr,
-      res.has_value() ? res->data_ptr() : nullptr, Bsz, M, K,
+      Y.data_ptr(), W.data_ptr(), X.data_ptr(), bp, rp, Bsz, M, K,
       cur_stream());
   TORCH_CHECK(rc == 0, "mtile_gemm: unsupported shape B=", Bsz, " K=", K,
               " M=", M);
@@ -816,37 +886,31 @@ void rope_prefill_append(torch::Tensor qkv, torch::Tensor kpool,
                          int64_t layer,
                          c10::optional<torch::Tensor> kscale,
                          c10::optional<torch::Tensor> vscale) {
-  check_bf16(qkv, "qkv");
-  const bool kv8 = kscale.has_value();
-  if (kv8) {
-    TORCH_CHECK(kpool.scalar_type() == torch::kUInt8 &&
-                    vpool.scalar_type() == torch::kUInt8,
-                "fp8 KV cache must be uint8 pools");
-    check_f32(*kscale, "kscale");
-    check_f32(*vscale, "vscale");
-  } else {
-    check_bf16(kpool, "kpool");
-    check_bf16(vpool, "vpool");
-  }
+  const PrefillGeom g =
+      check_prefill("rope_prefill_append", qkv, kpool, vpool, kscale, vscale,
+                    pos0, slot, layer);
   check_f32(cos_t, "cos");
   check_f32(sin_t, "sin");
-  const int n_layers_pool = (int)kpool.size(1);
-  const int n_kv = (int)kpool.size(2);
-  const int max_seq = (int)kpool.size(3);
-  const int hs = (int)kpool.size(4);
-  const int rope_ne = cos_t.dim() > 1 ? (int)cos_t.size(1) : 0;
-  TORCH_CHECK(qkv.dim() == 2, "qkv must be [T, qkv_dim]");
-  const int T = (int)qkv.size(0);
-  const int qpk = (int)qkv.size(1) / (n_kv * hs) - 2;
-  TORCH_CHECK((int64_t)pos0 + T <= max_seq, "prefill overflows the pool");
+  TORCH_CHECK(cos_t.sizes() == sin_t.sizes(),
+              "rope_prefill_append: cos and sin differ in shape");
+  // a 1-D (or zero-width) table switches rope off
+  const int64_t rope_ne = cos_t.dim() > 1 ? cos_t.size(1) : 0;
+  if (rope_ne > 0) {
+    TORCH_CHECK(cos_t.dim() == 2, "rope_prefill_append: cos must be 2-D");
+    TORCH_CHECK(rope_ne % 2 == 0 && rope_ne <= g.hs,
+                "rope_prefill_append: rope_ne must be even and <= head_size");
+    TORCH_CHECK(cos_t.size(0) >= pos0 + g.T,
+                "rope_prefill_append: the rope table has ", cos_t.size(0),
+                " rows, pos0 + T = ", pos0 + g.T);
+  }
   launch_rope_prefill_append(
       qkv.data_ptr(), kpool.data_ptr(), vpool.data_ptr(),
-      kv8 ? kscale->data_ptr<float>() : nullptr,
-      kv8 ? vscale->data_ptr<float>() : nullptr,
+      g.kv8 ? kscale->data_ptr<float>() : nullptr,
+      g.kv8 ? vscale->data_ptr<float>() : nullptr,
       rope_ne ? cos_t.data_ptr<float>() : nullptr,
       rope_ne ? sin_t.data_ptr<float>() : nullptr, (int)pos0, (int)slot,
-      (int)layer, n_layers_pool, n_kv, max_seq, hs, rope_ne, qpk, T,
-      cur_stream());
+      (int)layer, g.n_layers, g.n_kv, g.max_seq, g.hs, (int)rope_ne, g.qpk,
+      g.T, cur_stream());
 }
 
 void prefill_attn(torch::Tensor out, torch::Tensor qkv, torch::Tensor kpool,
@@ -855,32 +919,17 @@ void prefill_attn(torch::Tensor out, torch::Tensor qkv, torch::Tensor kpool,
                   c10::optional<torch::Tensor> kscale,
                   c10::optional<torch::Tensor> vscale) {
   check_bf16(out, "out");
-  check_bf16(qkv, "qkv");
-  const bool kv8 = kscale.has_value();
-  if (kv8) {
-    TORCH_CHECK(kpool.scalar_type() == torch::kUInt8 &&
-                    vpool.scalar_type() == torch::kUInt8,
-                "fp8 KV cache must be uint8 pools");
-    check_f32(*kscale, "kscale");
-    check_f32(*vscale, "vscale");
-  } else {
-    check_bf16(kpool, "kpool");
-    check_bf16(vpool, "vpool");
-  }
-  const int n_layers_pool = (int)kpool.size(1);
-  const int n_kv = (int)kpool.size(2);
-  const int max_seq = (int)kpool.size(3);
-  const int hs = (int)kpool.size(4);
-  const int T = (int)qkv.size(0);
-  const int qpk = (int)qkv.size(1) / (n_kv * hs) - 2;
-  TORCH_CHECK(out.numel() == (int64_t)T * n_kv * qpk * hs, "out size");
+  const PrefillGeom g = check_prefill("prefill_attn", qkv, kpool, vpool,
+                                      kscale, vscale, pos0, slot, layer);
+  TORCH_CHECK(out.numel() == (int64_t)g.T * g.n_kv * g.qpk * g.hs,
+              "out size");
   int rc = launch_prefill_attn(
       out.data_ptr(), qkv.data_ptr(), kpool.data_ptr(), vpool.data_ptr(),
-      kv8 ? kscale->data_ptr<float>() : nullptr,
-      kv8 ? vscale->data_ptr<float>() : nullptr,
-      (int)pos0, (int)slot, (int)layer, n_layers_pool, n_kv, max_seq, hs,
-      qpk, T, (float)scale, cur_stream());
-  TORCH_CHECK(rc == 0, "prefill_attn: unsupported head_size ", hs);
+      g.kv8 ? kscale->data_ptr<float>() : nullptr,
+      g.kv8 ? vscale->data_ptr<float>() : nullptr,
+      (int)pos0, (int)slot, (int)layer, g.n_layers, g.n_kv, g.max_seq, g.hs,
+      g.qpk, g.T, (float)scale, cur_stream());
+  TORCH_CHECK(rc == 0, "prefill_attn: unsupported head_size ", g.hs);
 }
 
 void add(torch::Tensor out, torch::Tensor a, torch::Tensor b) {

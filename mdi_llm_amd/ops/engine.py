@@ -93,7 +93,7 @@ def quantize_int4_groupwise(w: torch.Tensor):
     kernel computes it.  K is padded to Kp = ceil(K/128)*128 with zero
     nibbles (the padded positions take no part in a group's min/max).
 
-    Nibble order (what gemv_int4_kernel unpacks): each 8 consecutive k
+    Nibble order (what dot32_int4 unpacks): each 8 consecutive k
     form one little-endian 32-bit word whose low half holds the even k and
     whose high half the odd k: n0 | n2<<4 | n4<<8 | n6<<12 | n1<<16 |
     n3<<20 | n5<<24 | n7<<28, i.e. bytes (n0|n2<<4, n4|n6<<4, n1|n3<<4,

@@ -322,34 +322,14 @@ void gemv_int4(torch::Tensor out, torch::Tensor W, torch::Tensor qparams,
   check_bf16(x, "x");
   const int K = (int)x.numel();
   const int M = (int)out.numel();
-  TORCH_CHECK(M > 0 && K > 0, "empty GEMV");
+  check_gemv_dims(M, K, epilogue, norm_kind);
   TORCH_CHECK(K % 8 == 0, "K must be a multiple of 8");
   check_int4(W, qparams, M, K, "W");
-  const void* bp = nullptr;
-  const void* rp = nullptr;
-  const void* nwp = nullptr;
-  const void* nbp = nullptr;
-  if (bias.has_value()) {
-    check_bf16(*bias, "bias");
-    TORCH_CHECK(bias->numel() == M, "bias size");
-    bp = bias->data_ptr();
-  }
-  if (res.has_value()) {
-    check_bf16(*res, "res");
-    TORCH_CHECK(res->numel() == M, "res size");
-    rp = res->data_ptr();
-  }
-  if (norm_kind != 0) {
-    TORCH_CHECK(norm_w.has_value(), "norm_w required with norm_kind");
-    check_bf16(*norm_w, "norm_w");
-    TORCH_CHECK(norm_w->numel() == K, "norm_w size");
-    nwp = norm_w->data_ptr();
-    if (norm_b.has_value()) {
-      check_bf16(*norm_b, "norm_b");
-      TORCH_CHECK(norm_b->numel() == K, "norm_b size");
-      nbp = norm_b->data_ptr();
-    }
-  }
+  const void* bp = opt_bf16_vec(bias, M, "bias");
+  const void* rp = opt_bf16_vec(res, M, "res");
+  const NormPtrs np = check_norm(norm_w, norm_b, norm_kind, K);
+  const void* nwp = np.w;
+  const void* nbp = np.b;
   launch_gemv_int4(out.data_ptr(), W.data_ptr(), qparams.data_ptr(),
                    x.data_ptr(), bp, rp, nwp, nbp, (float)eps, M, K,
                    (int)epilogue, (int)norm_kind, (int)rows, cur_stream());
@@ -364,23 +344,13 @@ void gemv_swiglu_int4(torch::Tensor out, torch::Tensor Wg, torch::Tensor gq,
   check_bf16(x, "x");
   const int K = (int)x.numel();
   const int M = (int)out.numel();
-  TORCH_CHECK(M > 0 && K > 0, "empty GEMV");
+  check_gemv_dims(M, K, 0, norm_kind);
   TORCH_CHECK(K % 8 == 0, "K must be a multiple of 8");
   check_int4(Wg, gq, M, K, "Wg");
   check_int4(Wu, uq, M, K, "Wu");
-  const void* nwp = nullptr;
-  const void* nbp = nullptr;
-  if (norm_kind != 0) {
-    TORCH_CHECK(norm_w.has_value(), "norm_w required with norm_kind");
-    check_bf16(*norm_w, "norm_w");
-    TORCH_CHECK(norm_w->numel() == K, "norm_w size");
-    nwp = norm_w->data_ptr();
-    if (norm_b.has_value()) {
-      check_bf16(*norm_b, "norm_b");
-      TORCH_CHECK(norm_b->numel() == K, "norm_b size");
-      nbp = norm_b->data_ptr();
-    }
-  }
+  const NormPtrs np = check_norm(norm_w, norm_b, norm_kind, K);
+  const void* nwp = np.w;
+  const void* nbp = np.b;
   launch_gemv_swiglu_int4(out.data_ptr(), Wg.data_ptr(), gq.data_ptr(),
                           Wu.data_ptr(), uq.data_ptr(), x.data_ptr(), nwp,
                           nbp, (float)eps, M, K, gelu_gate ? 1 : 0,

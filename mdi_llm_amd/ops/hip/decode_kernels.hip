@@ -1,13 +1,13 @@
 // decode_kernels.hip — hand-written CDNA4 (gfx950 / MI355X) kernels for the
 // per-token decode path of mdi_llm_amd.
 //
-// These implement, natively for MI355X, the ops the reference runs through
-// PyTorch/cuBLAS (survey §2.4; /root/reference/src/sub/model.py): RMSNorm /
+// These implement, natively for MI355X, the ops the reference model runs
+// through PyTorch/cuBLAS (survey §2.4): RMSNorm /
 // LayerNorm, the decode GEMVs (fused-QKV, attention proj, SwiGLU MLP, GELU
 // MLP, lm-head), RoPE + KV-cache append, and GQA flash-decode attention
 // (MFMA 16x16x32 bf16 QK^T with online softmax, split-S across workgroups).
 //
-// Design notes (per /opt/skills/guides/cdna_hip_programming.md):
+// Design notes (per the CDNA HIP programming guide):
 //  * wave = 64 lanes; all block sizes are multiples of 64.
 //  * bf16 global loads vectorized as int4 (16 B = 8 bf16 per lane).
 //  * decode GEMV streams weights once; x is staged in LDS per block.
@@ -246,10 +246,12 @@ __global__ void layernorm_kernel(bf16* __restrict__ out,
 // ---------------------------------------------------------------------------
 // Decode GEMV: out[M] = W[M,K] @ norm?(x)[K] (+ bias) (+ residual) (+ act)
 //
-// W row-major bf16, streamed once from HBM (the decode bound); x staged in
-// LDS (K*2 bytes, up to ~28 KiB for the 14336-wide MLP). Block = 256
-// threads = 4 waves; each wave owns TWO adjacent output rows per grid-stride
-// step (doubles load ILP); lane reads 16 B per row per iteration.
+// W row-major, streamed once from HBM (the decode bound); x staged in LDS
+// (K*2 bytes, up to ~28 KiB for the 14336-wide MLP). Block = 256 threads =
+// 4 waves; each wave owns ROWS adjacent output rows per grid-stride step
+// (more load ILP); lane reads 16 B per row per iteration.  The staged
+// skeletons (gemv_staged_kernel, gemv_swiglu_kernel) are written once and
+// take the weight format (bf16, fp8, int4) as a policy struct, see below.
 //
 // NORM fuses the pre-norm into the staging pass (saves a separate tiny
 // kernel + a global round-trip per call): after staging raw x, the block
@@ -341,86 +343,16 @@ DEVINL float stage_x(bf16* xs, const bf16* __restrict__ x,
   return 1.f;
 }
 
-template <int EPI, int NORM, int ROWS>
-__global__ void gemv_kernel(bf16* __restrict__ out,
-                            const bf16* __restrict__ W,
-                            const bf16* __restrict__ x,
-                            const bf16* __restrict__ bias,
-                            const bf16* __restrict__ res,
-                            const bf16* __restrict__ nw,
-                            const bf16* __restrict__ nb, float eps, int M,
-                            int K) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  __shared__ float red[8];
-  bf16* xs = reinterpret_cast<bf16*>(smem);
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
-  const int rows_per_grid = gridDim.x * (blockDim.x >> 6) * ROWS;
-  const int row0 = (blockIdx.x * (blockDim.x >> 6) + wave) * ROWS;
-
-  // Prefetch the first W chunk of the first row set BEFORE the staging
-  // barrier: plain global loads stay in flight across s_barrier, so HBM
-  // streams W while the block stages/normalizes x in LDS.
-  bf16x8 wpre[ROWS];
-  const bool pre_ok = lane * 8 < K;  // K is a multiple of 8
-#pragma unroll
-  for (int r = 0; r < ROWS; ++r)
-    if (pre_ok)
-      wpre[r] = load8_nt(W + (size_t)min(row0 + r, M - 1) * K + lane * 8);
-
-  const float nscale = stage_x<NORM>(xs, x, nw, nb, K, eps, red);
-
-  for (int row = row0; row < M; row += rows_per_grid) {
-    const bf16* wrow[ROWS];
-    float acc[ROWS];
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r) {
-      wrow[r] = W + (size_t)min(row + r, M - 1) * K;
-      acc[r] = 0.f;
-    }
-    int istart = lane * 8;
-    if (row == row0 && pre_ok) {
-      // peeled first chunk: consume the pre-barrier prefetch
-      bf16x8 xv = load8(xs + istart);
-#pragma unroll
-      for (int r = 0; r < ROWS; ++r) {
-        bf16x8 wv;
-        *reinterpret_cast<int4*>(wv.v) =
-            *reinterpret_cast<const int4*>(wpre[r].v);
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-          acc[r] += b2f(wv.v[j]) * b2f(xv.v[j]);
-      }
-      istart += 64 * 8;
-    }
-    for (int i = istart; i < K; i += 64 * 8) {
-      bf16x8 xv = load8(xs + i);
-#pragma unroll
-      for (int r = 0; r < ROWS; ++r) {
-        bf16x8 wv = load8_nt(wrow[r] + i);
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-          acc[r] += b2f(wv.v[j]) * b2f(xv.v[j]);
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r) acc[r] = wave_reduce_sum(acc[r]);
-    if (lane == 0) {
-#pragma unroll
-      for (int r = 0; r < ROWS; ++r) {
-        const int rw = row + r;
-        if (rw >= M) break;
-        float a = acc[r] * nscale;
-        if (bias != nullptr) a += b2f(bias[rw]);
-        if (EPI == 1 && res != nullptr) a += b2f(res[rw]);
-        if (EPI == 2) a = gelu_tanh(a);
-        if (EPI == 3) a = a / (1.f + expf(-a));
-        out[rw] = f2b(a);
-      }
-    }
-  }
+// Lane-0 tail of every single GEMV: a is the scaled dot product of row rw;
+// (+bias) (+residual) (activation) in fp32, then the one bf16 rounding.
+template <int EPI>
+DEVINL bf16 gemv_epilogue(float a, int rw, const bf16* bias,
+                          const bf16* res) {
+  if (bias != nullptr) a += b2f(bias[rw]);
+  if (EPI == 1 && res != nullptr) a += b2f(res[rw]);
+  if (EPI == 2) a = gelu_tanh(a);
+  if (EPI == 3) a = a / (1.f + expf(-a));
+  return f2b(a);
 }
 
 // Direct-x variant (NORM 0/1 only): no LDS staging, no barrier — the W
@@ -510,12 +442,7 @@ __global__ void gemv_direct_kernel(bf16* __restrict__ out,
       for (int r = 0; r < ROWS; ++r) {
         const int rw = row + r;
         if (rw >= M) break;
-        float a = acc[r] * nscale;
-        if (bias != nullptr) a += b2f(bias[rw]);
-        if (EPI == 1 && res != nullptr) a += b2f(res[rw]);
-        if (EPI == 2) a = gelu_tanh(a);
-        if (EPI == 3) a = a / (1.f + expf(-a));
-        out[rw] = f2b(a);
+        out[rw] = gemv_epilogue<EPI>(acc[r] * nscale, rw, bias, res);
       }
     }
   }
@@ -1236,139 +1163,6 @@ DEVINL float dot16_fp8(const unsigned* wq, const bf16* xs) {
   return acc;
 }
 
-// eidx/estride select an expert slab from stacked [n_slab, M, K] bytes and
-// its [n_slab, M] scales at launch-replay time (as gemv_direct_kernel); the
-// device-side index is clamped to the slabs that exist.
-template <int EPI, int NORM, int ROWS>
-__global__ void gemv_fp8_kernel(bf16* __restrict__ out,
-                                const unsigned char* __restrict__ W,
-                                const float* __restrict__ wscale,  // [M]
-                                const bf16* __restrict__ x,
-                                const bf16* __restrict__ bias,
-                                const bf16* __restrict__ res,
-                                const bf16* __restrict__ nw,
-                                const bf16* __restrict__ nb, float eps,
-                                int M, int K,
-                                const int* __restrict__ eidx,
-                                long long estride, int n_slab) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  __shared__ float red[8];
-  bf16* xs = reinterpret_cast<bf16*>(smem);
-  if (eidx != nullptr) {
-    const int e = min(max(eidx[0], 0), n_slab - 1);
-    W += (size_t)e * (size_t)estride;
-    wscale += (size_t)e * M;
-  }
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
-  const int rows_per_grid = gridDim.x * (blockDim.x >> 6) * ROWS;
-  const int row0 = (blockIdx.x * (blockDim.x >> 6) + wave) * ROWS;
-
-  // prefetch across the staging barrier (16 fp8 = one dwordx4 per lane)
-  i32x4_t wpre[ROWS];
-  const bool pre_ok = lane * 16 < K;
-#pragma unroll
-  for (int r = 0; r < ROWS; ++r)
-    if (pre_ok)
-      wpre[r] = load16_nt_u8(W + (size_t)min(row0 + r, M - 1) * K +
-                             lane * 16);
-
-  const float nscale = stage_x<NORM>(xs, x, nw, nb, K, eps, red);
-
-  for (int row = row0; row < M; row += rows_per_grid) {
-    const unsigned char* wrow[ROWS];
-    float acc[ROWS];
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r) {
-      wrow[r] = W + (size_t)min(row + r, M - 1) * K;
-      acc[r] = 0.f;
-    }
-    int istart = lane * 16;
-    if (row == row0 && pre_ok) {
-#pragma unroll
-      for (int r = 0; r < ROWS; ++r)
-        acc[r] += dot16_fp8(reinterpret_cast<const unsigned*>(&wpre[r]),
-                            xs + istart);
-      istart += 64 * 16;
-    }
-    for (int i = istart; i < K; i += 64 * 16) {
-#pragma unroll
-      for (int r = 0; r < ROWS; ++r) {
-        const i32x4_t wq = load16_nt_u8(wrow[r] + i);
-        acc[r] += dot16_fp8(reinterpret_cast<const unsigned*>(&wq), xs + i);
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r) acc[r] = wave_reduce_sum(acc[r]);
-    if (lane == 0) {
-#pragma unroll
-      for (int r = 0; r < ROWS; ++r) {
-        const int rw = row + r;
-        if (rw >= M) break;
-        float a = acc[r] * nscale * wscale[rw];
-        if (bias != nullptr) a += b2f(bias[rw]);
-        if (EPI == 1 && res != nullptr) a += b2f(res[rw]);
-        if (EPI == 2) a = gelu_tanh(a);
-        if (EPI == 3) a = a / (1.f + expf(-a));
-        out[rw] = f2b(a);
-      }
-    }
-  }
-}
-
-template <int NORM>
-__global__ void gemv_swiglu_fp8_kernel(
-    bf16* __restrict__ out, const unsigned char* __restrict__ Wg,
-    const float* __restrict__ gscale, const unsigned char* __restrict__ Wu,
-    const float* __restrict__ uscale, const bf16* __restrict__ x,
-    const bf16* __restrict__ nw, const bf16* __restrict__ nb, float eps,
-    int M, int K, int gelu_gate, const int* __restrict__ eidx,
-    long long estride, int n_slab, const float* __restrict__ escale) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  __shared__ float red[8];
-  bf16* xs = reinterpret_cast<bf16*>(smem);
-  if (eidx != nullptr) {  // expert slab + its row scales (see gemv_fp8)
-    const int e = min(max(eidx[0], 0), n_slab - 1);
-    const size_t off = (size_t)e * (size_t)estride;
-    Wg += off;
-    Wu += off;
-    gscale += (size_t)e * M;
-    uscale += (size_t)e * M;
-  }
-  const float oscale = (escale != nullptr) ? escale[0] : 1.f;
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
-  const int waves_per_grid = gridDim.x * (blockDim.x >> 6);
-  const int row0 = blockIdx.x * (blockDim.x >> 6) + wave;
-
-  const float nscale = stage_x<NORM>(xs, x, nw, nb, K, eps, red);
-
-  for (int row = row0; row < M; row += waves_per_grid) {
-    const unsigned char* grow = Wg + (size_t)row * K;
-    const unsigned char* urow = Wu + (size_t)row * K;
-    float ga = 0.f, ua = 0.f;
-    for (int i = lane * 16; i < K; i += 64 * 16) {
-      const i32x4_t gq = load16_nt_u8(grow + i);
-      const i32x4_t uq = load16_nt_u8(urow + i);
-      ga += dot16_fp8(reinterpret_cast<const unsigned*>(&gq), xs + i);
-      ua += dot16_fp8(reinterpret_cast<const unsigned*>(&uq), xs + i);
-    }
-    ga = wave_reduce_sum(ga) * nscale;
-    ua = wave_reduce_sum(ua) * nscale;
-    if (lane == 0) {
-      ga *= gscale[row];
-      ua *= uscale[row];
-      float act = gelu_gate ? gelu_tanh(ga) : ga / (1.f + expf(-ga));
-      // routing weight in fp32 before the bf16 rounding (as gemv_swiglu)
-      out[row] = f2b(act * ua * oscale);
-    }
-  }
-}
-
 // ---------------------------------------------------------------------------
 // INT4 group-quantized weight variants: 128 consecutive k share one bf16
 // (scale, zero) pair, w = nib * scale + zero.  Rows are zero-padded to
@@ -1449,23 +1243,161 @@ DEVINL float dot32_int4(const i32x4_t wq, const x32w& x, unsigned qp,
   return scale * (d0 + d1) + 0.25f * (zero - 128.f * scale) * gsum;
 }
 
-template <int EPI, int NORM, int ROWS>
-__global__ void gemv_int4_kernel(bf16* __restrict__ out,
-                                 const unsigned char* __restrict__ W,
-                                 const unsigned* __restrict__ qparams,
-                                 const bf16* __restrict__ x,
-                                 const bf16* __restrict__ bias,
-                                 const bf16* __restrict__ res,
-                                 const bf16* __restrict__ nw,
-                                 const bf16* __restrict__ nb, float eps,
-                                 int M, int K) {
+// ---------------------------------------------------------------------------
+// Weight formats of the staged GEMVs.  The two skeletons below are written
+// once; a format struct carries exactly what differs between bf16, fp8 and
+// int4 weights.  Offsets and strides are in the format's own units (elem_t):
+//   chunk_t / STEP   one lane's 16 B of weights, and how far it reaches
+//   xchunk_t         the staged x (and context) that chunk is dotted with
+//   stride(K)        row stride, also the bound of the chunk loop
+//   stage_extra      staging the format needs after stage_x
+//   load / load_x    non-temporal weight chunk / its staged x
+//   aux_row          the row's side data as accum wants it
+//   accum            acc += chunk . x, in the format's fixed operation order
+//   row_scale        per-row factor applied after the norm post-scale
+//   slab / slab_aux  expert-slab index read from eidx, and the side data's
+//                    offset for it (formats with SLABS only)
+// ---------------------------------------------------------------------------
+struct FmtBf16 {
+  using elem_t = bf16;
+  using aux_t = void;  // no side data
+  using chunk_t = bf16x8;
+  using xchunk_t = bf16x8;
+  static constexpr int STEP = 8;  // 8 k per chunk
+  static constexpr bool SLABS = true;
+  static constexpr bool SWIGLU_PREFETCH = true;
+  static int smem_bytes(int K) { return K * (int)sizeof(bf16); }
+  static DEVINL int stride(int K) { return K; }  // K is a multiple of 8
+  static DEVINL void stage_extra(bf16*, int) {}
+  static DEVINL chunk_t load(const bf16* p) { return load8_nt(p); }
+  static DEVINL xchunk_t load_x(const bf16* xs, int, int i) {
+    return load8(xs + i);
+  }
+  static DEVINL const void* aux_row(const void*, size_t, int) {
+    return nullptr;
+  }
+  static DEVINL void accum(float& acc, const chunk_t& w, const xchunk_t& x,
+                           const void*) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc += b2f(w.v[j]) * b2f(x.v[j]);
+  }
+  static DEVINL float row_scale(float a, const void*, int) { return a; }
+  // the index is used as it comes, as in gemv_direct_kernel
+  static DEVINL int slab(const int* eidx, int) { return eidx[0]; }
+  static DEVINL const void* slab_aux(const void* aux, int, int) {
+    return aux;
+  }
+};
+
+// aux = wscale[M], one fp32 scale per output row
+struct FmtFp8 {
+  using elem_t = unsigned char;
+  using aux_t = float;
+  using chunk_t = i32x4_t;
+  using xchunk_t = const bf16*;  // dot16_fp8 reads LDS itself
+  static constexpr int STEP = 16;  // 16 k per chunk
+  static constexpr bool SLABS = true;
+  // with the prefetched pair the fp8 SwiGLU compiles to 114 VGPRs instead
+  // of 68, occupancy 4 instead of 7 (profiles/gemv_skeleton.md)
+  static constexpr bool SWIGLU_PREFETCH = false;
+  static int smem_bytes(int K) { return K * (int)sizeof(bf16); }
+  static DEVINL int stride(int K) { return K; }
+  static DEVINL void stage_extra(bf16*, int) {}
+  static DEVINL chunk_t load(const unsigned char* p) {
+    return load16_nt_u8(p);
+  }
+  static DEVINL xchunk_t load_x(const bf16* xs, int, int i) {
+    return xs + i;
+  }
+  static DEVINL const float* aux_row(const float* aux, size_t, int) {
+    return aux;
+  }
+  static DEVINL void accum(float& acc, const chunk_t& w, xchunk_t x,
+                           const float*) {
+    acc += dot16_fp8(reinterpret_cast<const unsigned*>(&w), x);
+  }
+  static DEVINL float row_scale(float a, const float* wscale, int rw) {
+    return a * wscale[rw];
+  }
+  // the device-side index is clamped to the slabs that exist; the scales
+  // are stacked [n_slab, M] next to the [n_slab, M, K] bytes
+  static DEVINL int slab(const int* eidx, int n_slab) {
+    return min(max(eidx[0], 0), n_slab - 1);
+  }
+  static DEVINL const float* slab_aux(const float* aux, int e, int M) {
+    return aux + (size_t)e * M;
+  }
+};
+
+// LDS: Kp staged x (bf16) + one fp32 x-sum per 128-group
+static inline int int4_smem(int K) {
+  const int Kp = (K + 127) & ~127;
+  return Kp * (int)sizeof(bf16) + (Kp / 128) * (int)sizeof(float);
+}
+
+// aux = qparams[M][Kp/128], the groups' (scale | zero << 16) pairs; offsets
+// and strides are packed bytes (two k each)
+struct FmtInt4 {
+  using elem_t = unsigned char;
+  using aux_t = unsigned;
+  using chunk_t = i32x4_t;
+  struct xchunk_t {
+    x32w xv;
+    int g;       // the chunk's group
+    float gsum;  // and that group's sum of x
+  };
+  static constexpr int STEP = 16;  // 32 k per chunk
+  static constexpr bool SLABS = false;
+  static constexpr bool SWIGLU_PREFETCH = true;
+  static int smem_bytes(int K) { return int4_smem(K); }
+  static DEVINL int padded(int K) { return (K + 127) & ~127; }
+  static DEVINL int stride(int K) { return padded(K) >> 1; }
+  static DEVINL float* group_sums(bf16* xs, int K) {  // behind the x
+    return reinterpret_cast<float*>(xs + padded(K));
+  }
+  static DEVINL void stage_extra(bf16* xs, int K) {
+    stage_group_sums(xs, group_sums(xs, K), K, padded(K));
+  }
+  static DEVINL chunk_t load(const unsigned char* p) {
+    return load16_nt_u8(p);
+  }
+  static DEVINL xchunk_t load_x(bf16* xs, int K, int i) {
+    const int g = i >> 6;
+    return {load_x32(xs + i * 2), g, group_sums(xs, K)[g]};
+  }
+  static DEVINL const unsigned* aux_row(const unsigned* qparams, size_t rw,
+                                        int K) {
+    return qparams + rw * (padded(K) >> 7);
+  }
+  static DEVINL void accum(float& acc, const chunk_t& w, const xchunk_t& x,
+                           const unsigned* qrow) {
+    acc += dot32_int4(w, x.xv, qrow[x.g], x.gsum);
+  }
+  static DEVINL float row_scale(float a, const unsigned*, int) { return a; }
+};
+
+// Staged single GEMV.  eidx/estride select an expert slab from stacked
+// [n_slab, M, K] weights AT LAUNCH-REPLAY TIME (the index lives in device
+// memory, so MoE routing stays inside a captured graph).
+template <class Fmt, int EPI, int NORM, int ROWS>
+__global__ void gemv_staged_kernel(
+    bf16* __restrict__ out, const typename Fmt::elem_t* __restrict__ W,
+    const typename Fmt::aux_t* __restrict__ aux, const bf16* __restrict__ x,
+    const bf16* __restrict__ bias, const bf16* __restrict__ res,
+    const bf16* __restrict__ nw, const bf16* __restrict__ nb, float eps,
+    int M, int K, const int* __restrict__ eidx, long long estride,
+    int n_slab) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __shared__ float red[8];
-  const int Kp = (K + 127) & ~127;
-  const int rowb = Kp >> 1;  // packed bytes per row
-  const int ng = Kp >> 7;    // groups per row
   bf16* xs = reinterpret_cast<bf16*>(smem);
-  float* gs = reinterpret_cast<float*>(smem + (size_t)Kp * sizeof(bf16));
+  if constexpr (Fmt::SLABS) {
+    if (eidx != nullptr) {
+      const int e = Fmt::slab(eidx, n_slab);
+      W += (size_t)e * (size_t)estride;
+      aux = Fmt::slab_aux(aux, e, M);
+    }
+  }
+  const int stride = Fmt::stride(K);
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -1473,48 +1405,44 @@ __global__ void gemv_int4_kernel(bf16* __restrict__ out,
   const int rows_per_grid = gridDim.x * (blockDim.x >> 6) * ROWS;
   const int row0 = (blockIdx.x * (blockDim.x >> 6) + wave) * ROWS;
 
-  // prefetch across the staging barrier (32 nibbles = one dwordx4 per lane)
-  i32x4_t wpre[ROWS];
-  const bool pre_ok = lane * 16 < rowb;
+  // Prefetch the first W chunk of the first row set BEFORE the staging
+  // barrier: plain global loads stay in flight across s_barrier, so HBM
+  // streams W while the block stages/normalizes x in LDS.
+  typename Fmt::chunk_t wpre[ROWS];
+  const bool pre_ok = lane * Fmt::STEP < stride;
 #pragma unroll
   for (int r = 0; r < ROWS; ++r)
     if (pre_ok)
-      wpre[r] = load16_nt_u8(W + (size_t)min(row0 + r, M - 1) * rowb +
-                             lane * 16);
+      wpre[r] = Fmt::load(W + (size_t)min(row0 + r, M - 1) * stride +
+                          lane * Fmt::STEP);
 
   const float nscale = stage_x<NORM>(xs, x, nw, nb, K, eps, red);
-  stage_group_sums(xs, gs, K, Kp);
+  Fmt::stage_extra(xs, K);
 
   for (int row = row0; row < M; row += rows_per_grid) {
-    const unsigned char* wrow[ROWS];
-    const unsigned* qrow[ROWS];
+    const typename Fmt::elem_t* wrow[ROWS];
+    const typename Fmt::aux_t* arow[ROWS];
     float acc[ROWS];
 #pragma unroll
     for (int r = 0; r < ROWS; ++r) {
       const size_t rw = (size_t)min(row + r, M - 1);
-      wrow[r] = W + rw * rowb;
-      qrow[r] = qparams + rw * ng;
+      wrow[r] = W + rw * stride;
+      arow[r] = Fmt::aux_row(aux, rw, K);
       acc[r] = 0.f;
     }
-    int istart = lane * 16;
+    int istart = lane * Fmt::STEP;
     if (row == row0 && pre_ok) {
-      const x32w xv = load_x32(xs + istart * 2);
-      const int g = istart >> 6;
-      const float gsum = gs[g];
+      // peeled first chunk: consume the pre-barrier prefetch
+      const typename Fmt::xchunk_t xv = Fmt::load_x(xs, K, istart);
+#pragma unroll
+      for (int r = 0; r < ROWS; ++r) Fmt::accum(acc[r], wpre[r], xv, arow[r]);
+      istart += 64 * Fmt::STEP;
+    }
+    for (int i = istart; i < stride; i += 64 * Fmt::STEP) {
+      const typename Fmt::xchunk_t xv = Fmt::load_x(xs, K, i);
 #pragma unroll
       for (int r = 0; r < ROWS; ++r)
-        acc[r] += dot32_int4(wpre[r], xv, qrow[r][g], gsum);
-      istart += 64 * 16;
-    }
-    for (int i = istart; i < rowb; i += 64 * 16) {
-      const x32w xv = load_x32(xs + i * 2);
-      const int g = i >> 6;
-      const float gsum = gs[g];
-#pragma unroll
-      for (int r = 0; r < ROWS; ++r) {
-        const i32x4_t wq = load16_nt_u8(wrow[r] + i);
-        acc[r] += dot32_int4(wq, xv, qrow[r][g], gsum);
-      }
+        Fmt::accum(acc[r], Fmt::load(wrow[r] + i), xv, arow[r]);
     }
 #pragma unroll
     for (int r = 0; r < ROWS; ++r) acc[r] = wave_reduce_sum(acc[r]);
@@ -1523,108 +1451,41 @@ __global__ void gemv_int4_kernel(bf16* __restrict__ out,
       for (int r = 0; r < ROWS; ++r) {
         const int rw = row + r;
         if (rw >= M) break;
-        float a = acc[r] * nscale;
-        if (bias != nullptr) a += b2f(bias[rw]);
-        if (EPI == 1 && res != nullptr) a += b2f(res[rw]);
-        if (EPI == 2) a = gelu_tanh(a);
-        if (EPI == 3) a = a / (1.f + expf(-a));
-        out[rw] = f2b(a);
+        out[rw] = gemv_epilogue<EPI>(
+            Fmt::row_scale(acc[r] * nscale, aux, rw), rw, bias, res);
       }
-    }
-  }
-}
-
-template <int NORM>
-__global__ void gemv_swiglu_int4_kernel(
-    bf16* __restrict__ out, const unsigned char* __restrict__ Wg,
-    const unsigned* __restrict__ gqp, const unsigned char* __restrict__ Wu,
-    const unsigned* __restrict__ uqp, const bf16* __restrict__ x,
-    const bf16* __restrict__ nw, const bf16* __restrict__ nb, float eps,
-    int M, int K, int gelu_gate) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  __shared__ float red[8];
-  const int Kp = (K + 127) & ~127;
-  const int rowb = Kp >> 1;
-  const int ng = Kp >> 7;
-  bf16* xs = reinterpret_cast<bf16*>(smem);
-  float* gs = reinterpret_cast<float*>(smem + (size_t)Kp * sizeof(bf16));
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
-  const int waves_per_grid = gridDim.x * (blockDim.x >> 6);
-  const int row0 = blockIdx.x * (blockDim.x >> 6) + wave;
-
-  // prefetch across the staging barrier
-  i32x4_t gpre, upre;
-  const bool pre_ok = lane * 16 < rowb;
-  if (pre_ok) {
-    const size_t rw = (size_t)min(row0, M - 1);
-    gpre = load16_nt_u8(Wg + rw * rowb + lane * 16);
-    upre = load16_nt_u8(Wu + rw * rowb + lane * 16);
-  }
-
-  const float nscale = stage_x<NORM>(xs, x, nw, nb, K, eps, red);
-  stage_group_sums(xs, gs, K, Kp);
-
-  for (int row = row0; row < M; row += waves_per_grid) {
-    const unsigned char* grow = Wg + (size_t)row * rowb;
-    const unsigned char* urow = Wu + (size_t)row * rowb;
-    const unsigned* gq = gqp + (size_t)row * ng;
-    const unsigned* uq = uqp + (size_t)row * ng;
-    float ga = 0.f, ua = 0.f;
-    int istart = lane * 16;
-    if (row == row0 && pre_ok) {
-      const x32w xv = load_x32(xs + istart * 2);
-      const int g = istart >> 6;
-      const float gsum = gs[g];
-      ga += dot32_int4(gpre, xv, gq[g], gsum);
-      ua += dot32_int4(upre, xv, uq[g], gsum);
-      istart += 64 * 16;
-    }
-    for (int i = istart; i < rowb; i += 64 * 16) {
-      const i32x4_t gw = load16_nt_u8(grow + i);
-      const i32x4_t uw = load16_nt_u8(urow + i);
-      const x32w xv = load_x32(xs + i * 2);
-      const int g = i >> 6;
-      const float gsum = gs[g];
-      ga += dot32_int4(gw, xv, gq[g], gsum);
-      ua += dot32_int4(uw, xv, uq[g], gsum);
-    }
-    ga = wave_reduce_sum(ga) * nscale;
-    ua = wave_reduce_sum(ua) * nscale;
-    if (lane == 0) {
-      float act = gelu_gate ? gelu_tanh(ga) : ga / (1.f + expf(-ga));
-      out[row] = f2b(act * ua);
     }
   }
 }
 
 // SwiGLU pair GEMV: out[i] = silu(Wg_i . xn) * (Wu_i . xn), optional fused
-// pre-norm like gemv_kernel.  eidx/estride select an expert weight slab
-// from stacked [n_expert, M, K] tensors AT LAUNCH-REPLAY TIME (the index
-// lives in device memory, so MoE routing stays inside a captured graph);
-// escale multiplies the output by the routing weight.
-template <int NORM>
-__global__ void gemv_swiglu_kernel(bf16* __restrict__ out,
-                                   const bf16* __restrict__ Wg,
-                                   const bf16* __restrict__ Wu,
-                                   const bf16* __restrict__ x,
-                                   const bf16* __restrict__ nw,
-                                   const bf16* __restrict__ nb, float eps,
-                                   int M, int K, int gelu_gate,
-                                   const int* __restrict__ eidx,
-                                   long long estride,
-                                   const float* __restrict__ escale) {
+// pre-norm and expert slab like gemv_staged_kernel; escale multiplies the
+// output by the routing weight.  PREFETCH (Fmt::SWIGLU_PREFETCH) keeps the
+// first chunk of both rows in flight across the staging barrier.
+template <class Fmt, int NORM, bool PREFETCH>
+__global__ void gemv_swiglu_kernel(
+    bf16* __restrict__ out, const typename Fmt::elem_t* __restrict__ Wg,
+    const typename Fmt::aux_t* __restrict__ gaux,
+    const typename Fmt::elem_t* __restrict__ Wu,
+    const typename Fmt::aux_t* __restrict__ uaux, const bf16* __restrict__ x,
+    const bf16* __restrict__ nw, const bf16* __restrict__ nb, float eps,
+    int M, int K, int gelu_gate, const int* __restrict__ eidx,
+    long long estride, int n_slab, const float* __restrict__ escale) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __shared__ float red[8];
   bf16* xs = reinterpret_cast<bf16*>(smem);
-  if (eidx != nullptr) {
-    const size_t off = (size_t)eidx[0] * (size_t)estride;
-    Wg += off;
-    Wu += off;
+  if constexpr (Fmt::SLABS) {
+    if (eidx != nullptr) {
+      const int e = Fmt::slab(eidx, n_slab);
+      const size_t off = (size_t)e * (size_t)estride;
+      Wg += off;
+      Wu += off;
+      gaux = Fmt::slab_aux(gaux, e, M);
+      uaux = Fmt::slab_aux(uaux, e, M);
+    }
   }
   const float oscale = (escale != nullptr) ? escale[0] : 1.f;
+  const int stride = Fmt::stride(K);
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -1632,47 +1493,45 @@ __global__ void gemv_swiglu_kernel(bf16* __restrict__ out,
   const int waves_per_grid = gridDim.x * (blockDim.x >> 6);
   const int row0 = blockIdx.x * (blockDim.x >> 6) + wave;
 
-  // W prefetch across the staging barrier (see gemv_kernel)
-  const int rp0 = min(row0, M - 1);
-  const bool pre_ok = lane * 8 < K;
-  bf16x8 gpre, upre;
+  // W prefetch across the staging barrier (see gemv_staged_kernel)
+  const size_t rp0 = (size_t)min(row0, M - 1);
+  const bool pre_ok = PREFETCH && lane * Fmt::STEP < stride;
+  typename Fmt::chunk_t gpre, upre;
   if (pre_ok) {
-    gpre = load8_nt(Wg + (size_t)rp0 * K + lane * 8);
-    upre = load8_nt(Wu + (size_t)rp0 * K + lane * 8);
+    gpre = Fmt::load(Wg + rp0 * stride + lane * Fmt::STEP);
+    upre = Fmt::load(Wu + rp0 * stride + lane * Fmt::STEP);
   }
 
   const float nscale = stage_x<NORM>(xs, x, nw, nb, K, eps, red);
+  Fmt::stage_extra(xs, K);
 
   for (int row = row0; row < M; row += waves_per_grid) {
-    const bf16* grow = Wg + (size_t)row * K;
-    const bf16* urow = Wu + (size_t)row * K;
+    const typename Fmt::elem_t* grow = Wg + (size_t)row * stride;
+    const typename Fmt::elem_t* urow = Wu + (size_t)row * stride;
+    const typename Fmt::aux_t* gq = Fmt::aux_row(gaux, (size_t)row, K);
+    const typename Fmt::aux_t* uq = Fmt::aux_row(uaux, (size_t)row, K);
     float ga = 0.f, ua = 0.f;
-    int istart = lane * 8;
+    int istart = lane * Fmt::STEP;
     if (row == row0 && pre_ok) {
-      bf16x8 xv = load8(xs + istart);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        float xf = b2f(xv.v[j]);
-        ga += b2f(gpre.v[j]) * xf;
-        ua += b2f(upre.v[j]) * xf;
-      }
-      istart += 64 * 8;
+      const typename Fmt::xchunk_t xv = Fmt::load_x(xs, K, istart);
+      Fmt::accum(ga, gpre, xv, gq);
+      Fmt::accum(ua, upre, xv, uq);
+      istart += 64 * Fmt::STEP;
     }
-    for (int i = istart; i < K; i += 64 * 8) {
-      bf16x8 gv = load8_nt(grow + i);
-      bf16x8 uv = load8_nt(urow + i);
-      bf16x8 xv = load8(xs + i);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        float xf = b2f(xv.v[j]);
-        ga += b2f(gv.v[j]) * xf;
-        ua += b2f(uv.v[j]) * xf;
-      }
+    for (int i = istart; i < stride; i += 64 * Fmt::STEP) {
+      const typename Fmt::chunk_t gw = Fmt::load(grow + i);
+      const typename Fmt::chunk_t uw = Fmt::load(urow + i);
+      const typename Fmt::xchunk_t xv = Fmt::load_x(xs, K, i);
+      Fmt::accum(ga, gw, xv, gq);
+      Fmt::accum(ua, uw, xv, uq);
     }
     ga = wave_reduce_sum(ga) * nscale;
     ua = wave_reduce_sum(ua) * nscale;
     if (lane == 0) {
+      ga = Fmt::row_scale(ga, gaux, row);
+      ua = Fmt::row_scale(ua, uaux, row);
       float act = gelu_gate ? gelu_tanh(ga) : ga / (1.f + expf(-ga));
+      // routing weight in fp32 before the bf16 rounding
       out[row] = f2b(act * ua * oscale);
     }
   }
@@ -3878,12 +3737,65 @@ void launch_layernorm(void* out, const void* x, const void* w, const void* b,
                      (const bf16*)b, n, eps);
 }
 
+// Turns the runtime (epilogue, norm_kind, rows) of a single GEMV into
+// template arguments, once for every weight format: f is called with three
+// integral constants (EPI, NORM, ROWS).  An out-of-range epilogue/norm_kind
+// runs as (0, 0); rows other than 2 and 4 run as 1.
+template <int V>
+using IC = std::integral_constant<int, V>;
+
+template <int E, int N, class F>
+static void gemv_dispatch_rows(int rows, F& f) {
+  if (rows == 4) f(IC<E>{}, IC<N>{}, IC<4>{});
+  else if (rows == 2) f(IC<E>{}, IC<N>{}, IC<2>{});
+  else f(IC<E>{}, IC<N>{}, IC<1>{});
+}
+
+template <class F>
+static void gemv_dispatch(int epilogue, int norm_kind, int rows, F f) {
+  switch (epilogue * 4 + norm_kind) {
+    case 1: return gemv_dispatch_rows<0, 1>(rows, f);
+    case 2: return gemv_dispatch_rows<0, 2>(rows, f);
+    case 4: return gemv_dispatch_rows<1, 0>(rows, f);
+    case 5: return gemv_dispatch_rows<1, 1>(rows, f);
+    case 6: return gemv_dispatch_rows<1, 2>(rows, f);
+    case 8: return gemv_dispatch_rows<2, 0>(rows, f);
+    case 9: return gemv_dispatch_rows<2, 1>(rows, f);
+    case 10: return gemv_dispatch_rows<2, 2>(rows, f);
+    case 12: return gemv_dispatch_rows<3, 0>(rows, f);
+    case 13: return gemv_dispatch_rows<3, 1>(rows, f);
+    case 14: return gemv_dispatch_rows<3, 2>(rows, f);
+    default: return gemv_dispatch_rows<0, 0>(rows, f);
+  }
+}
+
+// arguments of a staged single GEMV; aux is the format's side data
+struct GemvArgs {
+  void* out;
+  const void *W, *aux, *x, *bias, *res, *norm_w, *norm_b;
+  float eps;
+  int M, K;
+  const int* eidx;
+  long long estride;
+  int n_slab;
+};
+
+template <class Fmt, int E, int N, int R>
+static void launch_staged(dim3 grid, const GemvArgs& a, hipStream_t stream) {
+  hipLaunchKernelGGL((gemv_staged_kernel<Fmt, E, N, R>), grid, dim3(256),
+                     Fmt::smem_bytes(a.K), stream, (bf16*)a.out,
+                     (const typename Fmt::elem_t*)a.W,
+                     (const typename Fmt::aux_t*)a.aux, (const bf16*)a.x,
+                     (const bf16*)a.bias, (const bf16*)a.res,
+                     (const bf16*)a.norm_w, (const bf16*)a.norm_b, a.eps,
+                     a.M, a.K, a.eidx, a.estride, a.n_slab);
+}
+
 void launch_gemv(void* out, const void* W, const void* x, const void* bias,
                  const void* res, const void* norm_w, const void* norm_b,
                  float eps, int M, int K, int epilogue, int norm_kind,
                  int rows, const int* eidx, long long estride,
                  hipStream_t stream) {
-  const int smem = K * sizeof(bf16);
   if (rows == 0) rows = M >= 32768 ? 4 : (M > 8192 ? 2 : 1);
   dim3 grid(gemv_grid(M, 4 * rows)), block(256);
   // register-staged fused-RMS form for the qkv shape, grid shrunk so the
@@ -3909,51 +3821,38 @@ void launch_gemv(void* out, const void* W, const void* x, const void* bias,
                          (const bf16*)norm_w, eps, M, K);
     return;
   }
+  const GemvArgs a{out, W, nullptr, x, bias, res, norm_w, norm_b, eps, M, K,
+                   nullptr, 0, 0};  // the staged form takes no expert slab
   // NORM 0/1: the direct-x kernel (no staging barrier); 2: staged LDS form
-#define GEMV_CASE1(E, N, R)                                                 \
-  do {                                                                      \
-    if (N == 0 && K <= 6144 && R == 1)                                      \
-      hipLaunchKernelGGL((gemv_direct_kernel<E, N == 2 ? 0 : N, R, 4>),     \
-                         grid, block, 0, stream, (bf16*)out,                \
-                         (const bf16*)W, (const bf16*)x, (const bf16*)bias, \
-                         (const bf16*)res, (const bf16*)norm_w, eps, M, K,  \
-                         eidx, estride);                                    \
-    else if (N != 2)                                                        \
-      hipLaunchKernelGGL((gemv_direct_kernel<E, N == 2 ? 0 : N, R, 2>),     \
-                         grid, block, 0, stream, (bf16*)out,                \
-                         (const bf16*)W, (const bf16*)x, (const bf16*)bias, \
-                         (const bf16*)res, (const bf16*)norm_w, eps, M, K,  \
-                         eidx, estride);                                    \
-    else                                                                    \
-      hipLaunchKernelGGL((gemv_kernel<E, N, R>), grid, block, smem, stream, \
-                         (bf16*)out, (const bf16*)W, (const bf16*)x,        \
-                         (const bf16*)bias, (const bf16*)res,               \
-                         (const bf16*)norm_w, (const bf16*)norm_b, eps, M,  \
-                         K);                                                \
-  } while (0)
-#define GEMV_CASE(E, N)                                                     \
-  do {                                                                      \
-    if (rows == 4) GEMV_CASE1(E, N, 4);                                     \
-    else if (rows == 2) GEMV_CASE1(E, N, 2);                                \
-    else GEMV_CASE1(E, N, 1);                                               \
-  } while (0)
-  switch (epilogue * 4 + norm_kind) {
-    case 0: GEMV_CASE(0, 0); break;
-    case 1: GEMV_CASE(0, 1); break;
-    case 2: GEMV_CASE(0, 2); break;
-    case 4: GEMV_CASE(1, 0); break;
-    case 5: GEMV_CASE(1, 1); break;
-    case 6: GEMV_CASE(1, 2); break;
-    case 8: GEMV_CASE(2, 0); break;
-    case 9: GEMV_CASE(2, 1); break;
-    case 10: GEMV_CASE(2, 2); break;
-    case 12: GEMV_CASE(3, 0); break;
-    case 13: GEMV_CASE(3, 1); break;
-    case 14: GEMV_CASE(3, 2); break;
-    default: GEMV_CASE(0, 0);
-  }
-#undef GEMV_CASE
-#undef GEMV_CASE1
+  gemv_dispatch(epilogue, norm_kind, rows, [&](auto e, auto n, auto r) {
+    constexpr int E = decltype(e)::value, N = decltype(n)::value,
+                  R = decltype(r)::value;
+    if constexpr (N == 2) {
+      launch_staged<FmtBf16, E, N, R>(grid, a, stream);
+    } else if (N == 0 && K <= 6144 && R == 1) {
+      hipLaunchKernelGGL((gemv_direct_kernel<E, N, R, 4>), grid, block, 0,
+                         stream, (bf16*)out, (const bf16*)W, (const bf16*)x,
+                         (const bf16*)bias, (const bf16*)res,
+                         (const bf16*)norm_w, eps, M, K, eidx, estride);
+    } else {
+      hipLaunchKernelGGL((gemv_direct_kernel<E, N, R, 2>), grid, block, 0,
+                         stream, (bf16*)out, (const bf16*)W, (const bf16*)x,
+                         (const bf16*)bias, (const bf16*)res,
+                         (const bf16*)norm_w, eps, M, K, eidx, estride);
+    }
+  });
+}
+
+// fp8 and int4 single GEMVs: always the staged form
+template <class Fmt>
+static void launch_gemv_staged(const GemvArgs& a, int epilogue, int norm_kind,
+                               int rows, hipStream_t stream) {
+  if (rows == 0) rows = a.M >= 32768 ? 4 : (a.M > 8192 ? 2 : 1);
+  const dim3 grid(gemv_grid(a.M, 4 * rows));
+  gemv_dispatch(epilogue, norm_kind, rows, [&](auto e, auto n, auto r) {
+    launch_staged<Fmt, decltype(e)::value, decltype(n)::value,
+                  decltype(r)::value>(grid, a, stream);
+  });
 }
 
 void launch_gemv_fp8(void* out, const void* W, const float* wscale,
@@ -3962,38 +3861,45 @@ void launch_gemv_fp8(void* out, const void* W, const float* wscale,
                      int M, int K, int epilogue, int norm_kind, int rows,
                      const int* eidx, long long estride, int n_slab,
                      hipStream_t stream) {
-  const int smem = K * sizeof(bf16);
-  if (rows == 0) rows = M >= 32768 ? 4 : (M > 8192 ? 2 : 1);
-  dim3 grid(gemv_grid(M, 4 * rows)), block(256);
-#define GEMV8_CASE1(E, N, R)                                                \
-  hipLaunchKernelGGL((gemv_fp8_kernel<E, N, R>), grid, block, smem, stream, \
-                     (bf16*)out, (const unsigned char*)W, wscale,           \
-                     (const bf16*)x, (const bf16*)bias, (const bf16*)res,   \
-                     (const bf16*)norm_w, (const bf16*)norm_b, eps, M, K,   \
-                     eidx, estride, n_slab)
-#define GEMV8_CASE(E, N)                                                    \
-  do {                                                                      \
-    if (rows == 4) GEMV8_CASE1(E, N, 4);                                    \
-    else if (rows == 2) GEMV8_CASE1(E, N, 2);                               \
-    else GEMV8_CASE1(E, N, 1);                                              \
-  } while (0)
-  switch (epilogue * 4 + norm_kind) {
-    case 0: GEMV8_CASE(0, 0); break;
-    case 1: GEMV8_CASE(0, 1); break;
-    case 2: GEMV8_CASE(0, 2); break;
-    case 4: GEMV8_CASE(1, 0); break;
-    case 5: GEMV8_CASE(1, 1); break;
-    case 6: GEMV8_CASE(1, 2); break;
-    case 8: GEMV8_CASE(2, 0); break;
-    case 9: GEMV8_CASE(2, 1); break;
-    case 10: GEMV8_CASE(2, 2); break;
-    case 12: GEMV8_CASE(3, 0); break;
-    case 13: GEMV8_CASE(3, 1); break;
-    case 14: GEMV8_CASE(3, 2); break;
-    default: GEMV8_CASE(0, 0);
+  launch_gemv_staged<FmtFp8>({out, W, wscale, x, bias, res, norm_w, norm_b,
+                              eps, M, K, eidx, estride, n_slab},
+                             epilogue, norm_kind, rows, stream);
+}
+
+void launch_gemv_int4(void* out, const void* W, const void* qparams,
+                      const void* x, const void* bias, const void* res,
+                      const void* norm_w, const void* norm_b, float eps,
+                      int M, int K, int epilogue, int norm_kind, int rows,
+                      hipStream_t stream) {
+  launch_gemv_staged<FmtInt4>({out, W, qparams, x, bias, res, norm_w, norm_b,
+                               eps, M, K, nullptr, 0, 0},
+                              epilogue, norm_kind, rows, stream);
+}
+
+// the SwiGLU pair of any format; an out-of-range norm_kind runs as 0
+template <class Fmt>
+static void launch_swiglu(void* out, const void* Wg, const void* gaux,
+                          const void* Wu, const void* uaux, const void* x,
+                          const void* norm_w, const void* norm_b, float eps,
+                          int M, int K, int gelu_gate, int norm_kind,
+                          const int* eidx, long long estride, int n_slab,
+                          const float* escale, hipStream_t stream) {
+  using W_t = const typename Fmt::elem_t*;
+  using A_t = const typename Fmt::aux_t*;
+  auto go = [&](auto n) {
+    hipLaunchKernelGGL((gemv_swiglu_kernel<Fmt, decltype(n)::value,
+                                           Fmt::SWIGLU_PREFETCH>),
+                       dim3(gemv_grid(M, 4)), dim3(256), Fmt::smem_bytes(K),
+                       stream, (bf16*)out, (W_t)Wg, (A_t)gaux, (W_t)Wu,
+                       (A_t)uaux, (const bf16*)x, (const bf16*)norm_w,
+                       (const bf16*)norm_b, eps, M, K, gelu_gate, eidx,
+                       estride, n_slab, escale);
+  };
+  switch (norm_kind) {
+    case 1: go(IC<1>{}); break;
+    case 2: go(IC<2>{}); break;
+    default: go(IC<0>{});
   }
-#undef GEMV8_CASE
-#undef GEMV8_CASE1
 }
 
 void launch_gemv_swiglu_fp8(void* out, const void* Wg, const float* gscale,
@@ -4003,65 +3909,9 @@ void launch_gemv_swiglu_fp8(void* out, const void* Wg, const float* gscale,
                             int gelu_gate, int norm_kind, const int* eidx,
                             long long estride, int n_slab,
                             const float* escale, hipStream_t stream) {
-  const int smem = K * sizeof(bf16);
-  dim3 grid(gemv_grid(M, 4)), block(256);
-#define SW8_CASE(N)                                                         \
-  hipLaunchKernelGGL((gemv_swiglu_fp8_kernel<N>), grid, block, smem,        \
-                     stream, (bf16*)out, (const unsigned char*)Wg, gscale,  \
-                     (const unsigned char*)Wu, uscale, (const bf16*)x,      \
-                     (const bf16*)norm_w, (const bf16*)norm_b, eps, M, K,   \
-                     gelu_gate, eidx, estride, n_slab, escale)
-  switch (norm_kind) {
-    case 1: SW8_CASE(1); break;
-    case 2: SW8_CASE(2); break;
-    default: SW8_CASE(0);
-  }
-#undef SW8_CASE
-}
-
-// LDS: Kp staged x (bf16) + one fp32 x-sum per 128-group
-static inline int int4_smem(int K) {
-  const int Kp = (K + 127) & ~127;
-  return Kp * (int)sizeof(bf16) + (Kp / 128) * (int)sizeof(float);
-}
-
-void launch_gemv_int4(void* out, const void* W, const void* qparams,
-                      const void* x, const void* bias, const void* res,
-                      const void* norm_w, const void* norm_b, float eps,
-                      int M, int K, int epilogue, int norm_kind, int rows,
-                      hipStream_t stream) {
-  const int smem = int4_smem(K);
-  if (rows == 0) rows = M >= 32768 ? 4 : (M > 8192 ? 2 : 1);
-  dim3 grid(gemv_grid(M, 4 * rows)), block(256);
-#define GEMV4_CASE1(E, N, R)                                                \
-  hipLaunchKernelGGL((gemv_int4_kernel<E, N, R>), grid, block, smem,        \
-                     stream, (bf16*)out, (const unsigned char*)W,           \
-                     (const unsigned*)qparams, (const bf16*)x,              \
-                     (const bf16*)bias, (const bf16*)res,                   \
-                     (const bf16*)norm_w, (const bf16*)norm_b, eps, M, K)
-#define GEMV4_CASE(E, N)                                                    \
-  do {                                                                      \
-    if (rows == 4) GEMV4_CASE1(E, N, 4);                                    \
-    else if (rows == 2) GEMV4_CASE1(E, N, 2);                               \
-    else GEMV4_CASE1(E, N, 1);                                              \
-  } while (0)
-  switch (epilogue * 4 + norm_kind) {
-    case 0: GEMV4_CASE(0, 0); break;
-    case 1: GEMV4_CASE(0, 1); break;
-    case 2: GEMV4_CASE(0, 2); break;
-    case 4: GEMV4_CASE(1, 0); break;
-    case 5: GEMV4_CASE(1, 1); break;
-    case 6: GEMV4_CASE(1, 2); break;
-    case 8: GEMV4_CASE(2, 0); break;
-    case 9: GEMV4_CASE(2, 1); break;
-    case 10: GEMV4_CASE(2, 2); break;
-    case 12: GEMV4_CASE(3, 0); break;
-    case 13: GEMV4_CASE(3, 1); break;
-    case 14: GEMV4_CASE(3, 2); break;
-    default: GEMV4_CASE(0, 0);
-  }
-#undef GEMV4_CASE
-#undef GEMV4_CASE1
+  launch_swiglu<FmtFp8>(out, Wg, gscale, Wu, uscale, x, norm_w, norm_b, eps,
+                        M, K, gelu_gate, norm_kind, eidx, estride, n_slab,
+                        escale, stream);
 }
 
 void launch_gemv_swiglu_int4(void* out, const void* Wg, const void* gq,
@@ -4069,21 +3919,9 @@ void launch_gemv_swiglu_int4(void* out, const void* Wg, const void* gq,
                              const void* norm_w, const void* norm_b,
                              float eps, int M, int K, int gelu_gate,
                              int norm_kind, hipStream_t stream) {
-  const int smem = int4_smem(K);
-  dim3 grid(gemv_grid(M, 4)), block(256);
-#define SW4_CASE(N)                                                         \
-  hipLaunchKernelGGL((gemv_swiglu_int4_kernel<N>), grid, block, smem,       \
-                     stream, (bf16*)out, (const unsigned char*)Wg,          \
-                     (const unsigned*)gq, (const unsigned char*)Wu,         \
-                     (const unsigned*)uq, (const bf16*)x,                   \
-                     (const bf16*)norm_w, (const bf16*)norm_b, eps, M, K,   \
-                     gelu_gate)
-  switch (norm_kind) {
-    case 1: SW4_CASE(1); break;
-    case 2: SW4_CASE(2); break;
-    default: SW4_CASE(0);
-  }
-#undef SW4_CASE
+  launch_swiglu<FmtInt4>(out, Wg, gq, Wu, uq, x, norm_w, norm_b, eps, M, K,
+                         gelu_gate, norm_kind, nullptr, 0, 0, nullptr,
+                         stream);
 }
 
 void launch_gemv_swiglu(void* out, const void* Wg, const void* Wu,
@@ -4091,20 +3929,9 @@ void launch_gemv_swiglu(void* out, const void* Wg, const void* Wu,
                         float eps, int M, int K, int gelu_gate, int norm_kind,
                         const int* eidx, long long estride,
                         const float* escale, hipStream_t stream) {
-  const int smem = K * sizeof(bf16);
-  dim3 grid(gemv_grid(M, 4)), block(256);
-#define SW_CASE(N)                                                          \
-  hipLaunchKernelGGL((gemv_swiglu_kernel<N>), grid, block, smem, stream,    \
-                     (bf16*)out, (const bf16*)Wg, (const bf16*)Wu,          \
-                     (const bf16*)x, (const bf16*)norm_w,                   \
-                     (const bf16*)norm_b, eps, M, K, gelu_gate, eidx,       \
-                     estride, escale)
-  switch (norm_kind) {
-    case 1: SW_CASE(1); break;
-    case 2: SW_CASE(2); break;
-    default: SW_CASE(0);
-  }
-#undef SW_CASE
+  launch_swiglu<FmtBf16>(out, Wg, nullptr, Wu, nullptr, x, norm_w, norm_b,
+                         eps, M, K, gelu_gate, norm_kind, eidx, estride, 0,
+                         escale, stream);
 }
 
 void launch_swiglu_mul(void* out, const void* g, const void* u,

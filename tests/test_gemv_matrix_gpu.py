@@ -351,3 +351,20 @@ def test_empty_output_is_refused(ops):
     with pytest.raises(RuntimeError):
         ops.gemv_swiglu_fp8(o, _u8(0), _t(0, dtype=torch.float32), _u8(0),
                             _t(0, dtype=torch.float32), x, False)
+
+
+def test_int4_refuses_out_of_range_selectors(ops):
+    """An epilogue or norm_kind outside its range raises for int4 as for
+    bf16 and fp8 (it used to run as 0), before any launch."""
+    M, K = 8, 32
+    Wq, qp, x, nw = _u8(M, 64), _t(M, 1, 2), _t(K), _t(K)
+    buf = R.new_out_buffer(M, DEV)
+    o = buf[:M]
+    with pytest.raises(RuntimeError):
+        ops.gemv_int4(o, Wq, qp, x, None, None, 4)
+    with pytest.raises(RuntimeError):
+        ops.gemv_int4(o, Wq, qp, x, None, None, 0, nw, None, 3)
+    with pytest.raises(RuntimeError):
+        ops.gemv_swiglu_int4(o, Wq, qp, Wq, qp, x, False, nw, None, 3)
+    torch.cuda.synchronize()
+    assert bool((buf.float() == SENTINEL).all()), "something was launched"

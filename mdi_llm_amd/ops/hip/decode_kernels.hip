@@ -1636,7 +1636,13 @@ __global__ void rope_kv_append_kernel(
 }
 
 // ---------------------------------------------------------------------------
-// GQA flash-decode attention. Two variants share the MFMA tile core:
+// GQA flash-decode attention. Two variants (and the attention role of
+// attn_proj_kernel further down) use the same MFMA tile core.  Each kernel
+// carries its OWN COPY of it: q/k staging, K fragments, QK^T + masking,
+// the P*V row update and the append must be kept in step by hand.  Moving
+// them into shared DEVINL helpers changed register allocation and scratch
+// in most instantiations (profiles/attn_core.md), so only the host
+// dispatch (attn_geom_dispatch, AttnArgs) is shared so far.
 //
 //  * attn_decode_block_kernel — used when max_seq <= 4096 (chosen
 //    statically at launch, so hipGraphs stay shape-stable): ONE block per
@@ -1973,6 +1979,17 @@ __global__ void attn_decode_block_kernel(
 // ---------------------------------------------------------------------------
 typedef __attribute__((address_space(1))) unsigned int gu32_t;
 
+// dynamic-LDS layout of the attention role (byte offsets), for the kernel
+// and for the launcher's size
+template <int QPK, int HS>
+struct AttnProjLds {
+  static constexpr int q = 0;                              // [16 * HS] bf16
+  static constexpr int k_cur = 16 * HS * 2;                // [HS] bf16
+  static constexpr int o_part = (17 * HS * 2 + 15) & ~15;  // [4][QPK][HS]
+  static constexpr int ml_part = o_part + ATTN_WAVES * QPK * HS * 4;
+  static constexpr int total = ml_part + ATTN_WAVES * QPK * 2 * 4;
+};
+
 template <int QPK, int HS, int THROTTLE>
 __global__ void attn_proj_kernel(
     bf16* __restrict__ out,       // [M] = res + bias + W @ y
@@ -2118,13 +2135,14 @@ __global__ void attn_proj_kernel(
   }
 
   // --------------------------- attention role ---------------------------
-  // identical computation to attn_decode_block_kernel<QPK, HS, 0>, with
-  // the combine epilogue publishing granules instead of storing y
-  bf16* q_lds = reinterpret_cast<bf16*>(smem);      // [16 * HS] (swizzled)
-  bf16* k_cur = q_lds + 16 * head_size;             // [HS]
-  float* o_part = reinterpret_cast<float*>(
-      smem + ((17 * head_size * 2 + 15) & ~15));    // [4][QPK][HS]
-  float* ml_part = o_part + ATTN_WAVES * QPK * head_size;  // [4][QPK][2]
+  // a hand-kept copy of attn_decode_block_kernel<QPK, HS, 0> (flat LDS
+  // indexing, int2/int V loads for narrow ODIM), with the combine
+  // epilogue publishing granules instead of storing y
+  using Lds = AttnProjLds<QPK, HS>;
+  bf16* q_lds = reinterpret_cast<bf16*>(smem + Lds::q);  // swizzled
+  bf16* k_cur = reinterpret_cast<bf16*>(smem + Lds::k_cur);
+  float* o_part = reinterpret_cast<float*>(smem + Lds::o_part);
+  float* ml_part = reinterpret_cast<float*>(smem + Lds::ml_part);
 
   const int g = (int)blockIdx.x;
 
@@ -3538,147 +3556,6 @@ void launch_stage_slot(int* pos_out, int* token_out, const int* pos_table,
                      pos_table_mut, slot, adv_pos);
 }
 
-// fused attention+proj launcher.  Returns 0 on success, -1 when the
-// geometry has no instantiation (caller falls back to the split path).
-template <int QPK, int HS>
-static void attn_proj_dispatch2(void* out, const void* qkv, void* kpool,
-                                void* vpool, const float* cos_t,
-                                const float* sin_t, int rope_ne,
-                                const int* pos, const int* slot, int layer,
-                                int n_layers_pool, int n_kv_heads,
-                                int max_seq, float scale, const void* W,
-                                const void* bias, const void* res,
-                                void* gran, int M, hipStream_t stream) {
-  const int K = n_kv_heads * QPK * HS;
-  // rows per block group: fit every block resident at once (2 blocks/CU
-  // of 4 waves = the 8-wave/CU limit) AND the W tile in <=79 KB of LDS;
-  // grid-stride covers any remainder
-  // MDI_ATTN_PROJ_PB caps the number of proj (staging) blocks: fewer
-  // co-resident stagers leave the attention blocks' CUs unloaded (the
-  // "thin the loader while latency-sensitive work runs" principle,
-  // block-granular) at the cost of a longer-but-overlapped stage
-  static int pb_cap = -1;
-  if (pb_cap < 0) {
-    const char* e = getenv("MDI_ATTN_PROJ_PB");
-    pb_cap = e ? atoi(e) : 0;
-    if (pb_cap <= 0) pb_cap = 2 * 256;
-  }
-  const int cap_blocks =
-      (pb_cap < 2 * 256 ? pb_cap : 2 * 256) - n_kv_heads;
-  int BR = (M + cap_blocks - 1) / cap_blocks;
-  const int br_lds = (79 * 1024 - 16) / (K * 2);
-  if (br_lds < 1) return;  // K too large for the LDS tile (no instantiation)
-  if (BR > br_lds) BR = br_lds;
-  if (BR < 1) BR = 1;
-  int PB = (M + BR - 1) / BR;
-  if (PB > cap_blocks) PB = cap_blocks;
-  size_t smem_proj = (size_t)BR * K * 2 + 16;  // +verdict word
-  size_t smem_attn = (size_t)((17 * HS * 2 + 15) & ~15) +
-                     (size_t)ATTN_WAVES * QPK * HS * 4 +
-                     (size_t)ATTN_WAVES * QPK * 2 * 4;
-  size_t smem = smem_proj > smem_attn ? smem_proj : smem_attn;
-  static int thr = -1;
-  if (thr < 0) {
-    const char* e = getenv("MDI_ATTN_PROJ_SLEEP");
-    thr = e ? atoi(e) : 0;
-    if (thr != 0 && thr != 4 && thr != 8 && thr != 16) thr = 8;
-  }
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&attn_proj_kernel<QPK, HS, 0>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&attn_proj_kernel<QPK, HS, 4>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&attn_proj_kernel<QPK, HS, 8>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&attn_proj_kernel<QPK, HS, 16>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_set = true;
-  }
-#define AP_LAUNCH(T)                                                        \
-  hipLaunchKernelGGL((attn_proj_kernel<QPK, HS, T>),                        \
-                     dim3(n_kv_heads + PB), dim3(256), smem, stream,        \
-                     (bf16*)out, (const bf16*)qkv, (bf16*)kpool,            \
-                     (bf16*)vpool, cos_t, sin_t, rope_ne, pos, slot,        \
-                     layer, n_layers_pool, n_kv_heads, max_seq, scale,      \
-                     (const bf16*)W, (const bf16*)bias, (const bf16*)res,   \
-                     (unsigned int*)gran, M, BR)
-  if (thr == 0) AP_LAUNCH(0);
-  else if (thr == 4) AP_LAUNCH(4);
-  else if (thr == 8) AP_LAUNCH(8);
-  else AP_LAUNCH(16);
-#undef AP_LAUNCH
-}
-
-template <int QPK>
-static int attn_proj_dispatch1(int head_size, void* out, const void* qkv,
-                               void* kpool, void* vpool, const float* cos_t,
-                               const float* sin_t, int rope_ne,
-                               const int* pos, const int* slot, int layer,
-                               int n_layers_pool, int n_kv_heads,
-                               int max_seq, float scale, const void* W,
-                               const void* bias, const void* res, void* gran,
-                               int M, hipStream_t stream) {
-#define CASE_HS_P(H)                                                        \
-  if (head_size == H) {                                                     \
-    if constexpr (QPK * H >= 64) {                                          \
-      attn_proj_dispatch2<QPK, H>(out, qkv, kpool, vpool, cos_t, sin_t,     \
-                                  rope_ne, pos, slot, layer, n_layers_pool, \
-                                  n_kv_heads, max_seq, scale, W, bias, res, \
-                                  gran, M, stream);                         \
-      return 0;                                                             \
-    }                                                                       \
-  }
-  CASE_HS_P(64)
-  CASE_HS_P(128)
-  CASE_HS_P(256)
-#undef CASE_HS_P
-  return -1;
-}
-
-int launch_attn_proj(void* out, const void* qkv, void* kpool, void* vpool,
-                     const float* cos_t, const float* sin_t, int rope_ne,
-                     const int* pos, const int* slot, int layer,
-                     int n_layers_pool, int n_kv_heads, int max_seq,
-                     int head_size, int qpk, float scale, const void* W,
-                     const void* bias, const void* res, void* gran, int M,
-                     hipStream_t stream) {
-  if (max_seq > ATTN_BLOCK_MAX_SEQ) return -1;
-  switch (qpk) {
-    case 1:
-      return attn_proj_dispatch1<1>(head_size, out, qkv, kpool, vpool,
-                                    cos_t, sin_t, rope_ne, pos, slot, layer,
-                                    n_layers_pool, n_kv_heads, max_seq,
-                                    scale, W, bias, res, gran, M, stream);
-    case 2:
-      return attn_proj_dispatch1<2>(head_size, out, qkv, kpool, vpool,
-                                    cos_t, sin_t, rope_ne, pos, slot, layer,
-                                    n_layers_pool, n_kv_heads, max_seq,
-                                    scale, W, bias, res, gran, M, stream);
-    case 4:
-      return attn_proj_dispatch1<4>(head_size, out, qkv, kpool, vpool,
-                                    cos_t, sin_t, rope_ne, pos, slot, layer,
-                                    n_layers_pool, n_kv_heads, max_seq,
-                                    scale, W, bias, res, gran, M, stream);
-    case 8:
-      return attn_proj_dispatch1<8>(head_size, out, qkv, kpool, vpool,
-                                    cos_t, sin_t, rope_ne, pos, slot, layer,
-                                    n_layers_pool, n_kv_heads, max_seq,
-                                    scale, W, bias, res, gran, M, stream);
-    case 16:
-      return attn_proj_dispatch1<16>(head_size, out, qkv, kpool, vpool,
-                                     cos_t, sin_t, rope_ne, pos, slot,
-                                     layer, n_layers_pool, n_kv_heads,
-                                     max_seq, scale, W, bias, res, gran, M,
-                                     stream);
-  }
-  return -1;
-}
-
 // grouped M-tile GEMM launcher; returns -1 when the shape has no
 // instantiation (caller falls back to hipBLASLt)
 int launch_mtile_gemm(void* Y, const void* W, const void* X,
@@ -4053,87 +3930,68 @@ void launch_rope_kv_append(void* qkv, void* kpool, void* vpool,
                      max_seq, head_size, rope_n_elem, qpk);
 }
 
-template <int QPK, int HS>
-static void attn_dispatch2(void* out, float* part_o, float* part_ml,
-                           const void* qkv, void* kpool, void* vpool,
-                           float* kscale, float* vscale,
-                           const float* cos_t, const float* sin_t,
-                           int rope_ne, const int* pos, const int* slot,
-                           int layer, int n_layers_pool, int n_kv_heads,
-                           int max_seq, int n_chunks, float scale,
-                           int n_batch, int blocks, int force_split,
-                           hipStream_t stream) {
-  const int kv8 = kscale != nullptr;
-  // short/medium contexts: one block per (batch, kv_head), no global
-  // partials, no combine kernel — the whole attention step is ONE launch.
-  // MDI_ATTN_FORCE_SPLITS=1 forces the split-S + combine path instead
-  // (A/B knob: the round-2 split-S got block-cooperative staging and a
-  // parallel combine, so its short-S cost may have changed)
-  static int force_splits = -1;
-  if (force_splits < 0) {
-    const char* e = getenv("MDI_ATTN_FORCE_SPLITS");
-    force_splits = (e && e[0] == '1') ? 1 : 0;
+// Turns the runtime (qpk, head_size) of an attention launch into template
+// arguments: f is called with two integral constants (QPK, HS) for the 15
+// instantiated geometries; any other returns -1 with nothing launched.
+template <int QPK, class F>
+static int attn_geom_dispatch_hs(int head_size, F& f) {
+  switch (head_size) {
+    case 64: f(IC<QPK>{}, IC<64>{}); return 0;
+    case 128: f(IC<QPK>{}, IC<128>{}); return 0;
+    case 256: f(IC<QPK>{}, IC<256>{}); return 0;
   }
-  if (max_seq <= ATTN_BLOCK_MAX_SEQ && !force_splits && !force_split) {
-    const int nb = (n_batch > 0 ? n_batch : 1) * n_kv_heads;
-#define ATTN_BLK(BATCHV, KV8V, NBATCH)                                      \
-    hipLaunchKernelGGL((attn_decode_block_kernel<QPK, HS, BATCHV, KV8V>),   \
-                       dim3(nb), dim3(256), 0, stream, (bf16*)out,          \
-                       (const bf16*)qkv, kpool, vpool, kscale, vscale,      \
-                       cos_t, sin_t, rope_ne, pos, slot, layer,             \
-                       n_layers_pool, n_kv_heads, max_seq, scale, NBATCH)
-    if (n_batch > 0) {
-      if (kv8) ATTN_BLK(1, 1, n_batch);
-      else ATTN_BLK(1, 0, n_batch);
-    } else {
-      if (kv8) ATTN_BLK(0, 1, 1);
-      else ATTN_BLK(0, 0, 1);
-    }
-#undef ATTN_BLK
-    return;
-  }
-#define ATTN_SPL(BATCHV, KV8V, NBATCH)                                      \
-  hipLaunchKernelGGL((attn_decode_kernel<QPK, HS, BATCHV, KV8V>),           \
-                     dim3(blocks), dim3(256), 0, stream, part_o, part_ml,   \
-                     (const bf16*)qkv, kpool, vpool, kscale, vscale, cos_t, \
-                     sin_t, rope_ne, pos, slot, layer, n_layers_pool,       \
-                     n_kv_heads, max_seq, n_chunks, scale, NBATCH)
-  if (n_batch > 0) {
-    if (kv8) ATTN_SPL(1, 1, n_batch);
-    else ATTN_SPL(1, 0, n_batch);
-  } else {
-    if (kv8) ATTN_SPL(0, 1, 1);
-    else ATTN_SPL(0, 0, 1);
-  }
-#undef ATTN_SPL
+  return -1;
 }
 
-template <int QPK>
-static int attn_dispatch1(int head_size, void* out, float* part_o,
-                          float* part_ml, const void* qkv, void* kpool,
-                          void* vpool, float* kscale, float* vscale,
-                          const float* cos_t,
-                          const float* sin_t, int rope_ne, const int* pos,
-                          const int* slot, int layer, int n_layers_pool,
-                          int n_kv_heads, int max_seq, int n_chunks,
-                          float scale, int n_batch, int blocks,
-                          int force_split, hipStream_t stream) {
-#define CASE_HS(H)                                                          \
-  if (head_size == H) {                                                     \
-    if constexpr (QPK * H >= 64) {                                          \
-      attn_dispatch2<QPK, H>(out, part_o, part_ml, qkv, kpool, vpool,       \
-                             kscale, vscale, cos_t, sin_t, rope_ne, pos,    \
-                             slot, layer, n_layers_pool, n_kv_heads,        \
-                             max_seq, n_chunks, scale, n_batch, blocks,     \
-                             force_split, stream);                          \
-      return 0;                                                             \
-    }                                                                       \
+template <class F>
+static int attn_geom_dispatch(int qpk, int head_size, F f) {
+  switch (qpk) {
+    case 1: return attn_geom_dispatch_hs<1>(head_size, f);
+    case 2: return attn_geom_dispatch_hs<2>(head_size, f);
+    case 4: return attn_geom_dispatch_hs<4>(head_size, f);
+    case 8: return attn_geom_dispatch_hs<8>(head_size, f);
+    case 16: return attn_geom_dispatch_hs<16>(head_size, f);
   }
-  CASE_HS(64)
-  CASE_HS(128)
-  CASE_HS(256)
-#undef CASE_HS
-  return -1;  // unsupported geometry: caller falls back to the torch path
+  return -1;
+}
+
+// arguments every decode-attention launch forwards to its kernel
+struct AttnArgs {
+  void* out;
+  const void* qkv;
+  void *kpool, *vpool;
+  float *kscale, *vscale;  // fp8 KV row scales, or null for bf16 KV
+  const float *cos_t, *sin_t;
+  int rope_ne;
+  const int *pos, *slot;
+  int layer, n_layers_pool, n_kv_heads, max_seq;
+  float scale;
+};
+
+template <int QPK, int HS, int BATCH, int KV8>
+static void launch_attn_block(const AttnArgs& a, int n_batch,
+                              hipStream_t stream) {
+  const int nb = (BATCH ? n_batch : 1) * a.n_kv_heads;
+  hipLaunchKernelGGL((attn_decode_block_kernel<QPK, HS, BATCH, KV8>),
+                     dim3(nb), dim3(256), 0, stream, (bf16*)a.out,
+                     (const bf16*)a.qkv, a.kpool, a.vpool, a.kscale,
+                     a.vscale, a.cos_t, a.sin_t, a.rope_ne, a.pos, a.slot,
+                     a.layer, a.n_layers_pool, a.n_kv_heads, a.max_seq,
+                     a.scale, BATCH ? n_batch : 1);
+}
+
+template <int QPK, int HS, int BATCH, int KV8>
+static void launch_attn_split(const AttnArgs& a, float* part_o,
+                              float* part_ml, int n_chunks, int n_batch,
+                              hipStream_t stream) {
+  const int n_wg = a.n_kv_heads * n_chunks * (BATCH ? n_batch : 1);
+  const int blocks = (n_wg + ATTN_WAVES - 1) / ATTN_WAVES;
+  hipLaunchKernelGGL((attn_decode_kernel<QPK, HS, BATCH, KV8>), dim3(blocks),
+                     dim3(256), 0, stream, part_o, part_ml,
+                     (const bf16*)a.qkv, a.kpool, a.vpool, a.kscale,
+                     a.vscale, a.cos_t, a.sin_t, a.rope_ne, a.pos, a.slot,
+                     a.layer, a.n_layers_pool, a.n_kv_heads, a.max_seq,
+                     n_chunks, a.scale, BATCH ? n_batch : 1);
 }
 
 // returns 0 on success, -1 if (qpk, head_size) has no kernel instantiation
@@ -4146,56 +4004,40 @@ int launch_attn_decode(void* out, float* part_o, float* part_ml,
                        int n_layers_pool, int n_kv_heads, int max_seq,
                        int head_size, int qpk, int n_chunks, float scale,
                        int n_batch, int force_split, hipStream_t stream) {
-  const int n_wg = n_kv_heads * n_chunks * (n_batch > 0 ? n_batch : 1);
-  const int blocks = (n_wg + ATTN_WAVES - 1) / ATTN_WAVES;
-  int rc = -1;
-  switch (qpk) {
-    case 1:
-      rc = attn_dispatch1<1>(
-          head_size, out, part_o, part_ml, qkv, kpool, vpool, kscale,
-          vscale, cos_t, sin_t,
-          rope_ne, pos, slot, layer, n_layers_pool, n_kv_heads, max_seq,
-          n_chunks, scale, n_batch, blocks, force_split, stream);
-      break;
-    case 2:
-      rc = attn_dispatch1<2>(
-          head_size, out, part_o, part_ml, qkv, kpool, vpool, kscale,
-          vscale, cos_t, sin_t,
-          rope_ne, pos, slot, layer, n_layers_pool, n_kv_heads, max_seq,
-          n_chunks, scale, n_batch, blocks, force_split, stream);
-      break;
-    case 4:
-      rc = attn_dispatch1<4>(
-          head_size, out, part_o, part_ml, qkv, kpool, vpool, kscale,
-          vscale, cos_t, sin_t,
-          rope_ne, pos, slot, layer, n_layers_pool, n_kv_heads, max_seq,
-          n_chunks, scale, n_batch, blocks, force_split, stream);
-      break;
-    case 8:
-      rc = attn_dispatch1<8>(
-          head_size, out, part_o, part_ml, qkv, kpool, vpool, kscale,
-          vscale, cos_t, sin_t,
-          rope_ne, pos, slot, layer, n_layers_pool, n_kv_heads, max_seq,
-          n_chunks, scale, n_batch, blocks, force_split, stream);
-      break;
-    case 16:
-      rc = attn_dispatch1<16>(
-          head_size, out, part_o, part_ml, qkv, kpool, vpool, kscale,
-          vscale, cos_t, sin_t,
-          rope_ne, pos, slot, layer, n_layers_pool, n_kv_heads, max_seq,
-          n_chunks, scale, n_batch, blocks, force_split, stream);
-      break;
-    default:
-      return -1;
-  }
-  if (rc != 0) return rc;
-  static int force_splits2 = -1;
-  if (force_splits2 < 0) {
+  // short/medium contexts: one block per (batch, kv_head), no global
+  // partials, no combine kernel — the whole attention step is ONE launch.
+  // MDI_ATTN_FORCE_SPLITS=1 forces the split-S + combine path instead
+  // (A/B knob: the round-2 split-S got block-cooperative staging and a
+  // parallel combine, so its short-S cost may have changed)
+  static int force_splits = -1;
+  if (force_splits < 0) {
     const char* e = getenv("MDI_ATTN_FORCE_SPLITS");
-    force_splits2 = (e && e[0] == '1') ? 1 : 0;
+    force_splits = (e && e[0] == '1') ? 1 : 0;
   }
-  if (max_seq <= ATTN_BLOCK_MAX_SEQ && !force_splits2 && !force_split)
-    return 0;  // block-local: no combine
+  const bool split =
+      max_seq > ATTN_BLOCK_MAX_SEQ || force_splits || force_split;
+  const AttnArgs a{out, qkv, kpool, vpool, kscale, vscale, cos_t, sin_t,
+                   rope_ne, pos, slot, layer, n_layers_pool, n_kv_heads,
+                   max_seq, scale};
+  const int rc = attn_geom_dispatch(qpk, head_size, [&](auto q, auto h) {
+    constexpr int Q = decltype(q)::value, H = decltype(h)::value;
+    auto launch = [&](auto b, auto k) {
+      constexpr int B = decltype(b)::value, K8 = decltype(k)::value;
+      if (split)
+        launch_attn_split<Q, H, B, K8>(a, part_o, part_ml, n_chunks, n_batch,
+                                       stream);
+      else
+        launch_attn_block<Q, H, B, K8>(a, n_batch, stream);
+    };
+    if (n_batch > 0) {
+      if (kscale != nullptr) launch(IC<1>{}, IC<1>{});
+      else launch(IC<1>{}, IC<0>{});
+    } else {
+      if (kscale != nullptr) launch(IC<0>{}, IC<1>{});
+      else launch(IC<0>{}, IC<0>{});
+    }
+  });
+  if (rc != 0 || !split) return rc;  // block-local: no combine
   // the combine kernel is batch-agnostic: [B, n_head, chunks, hs] is just
   // B*n_head heads
   const int n_head_eff = n_kv_heads * qpk * (n_batch > 0 ? n_batch : 1);
@@ -4205,6 +4047,93 @@ int launch_attn_decode(void* out, float* part_o, float* part_ml,
                      stream, (bf16*)out, part_o, part_ml, n_chunks, head_size,
                      n_head_eff, pos, n_kv_heads * qpk);
   return 0;
+}
+
+template <int QPK, int HS, int THROTTLE>
+static void launch_attn_proj_thr(const AttnArgs& a, const void* W,
+                                 const void* bias, const void* res,
+                                 void* gran, int M, int BR, int PB,
+                                 size_t smem, hipStream_t stream) {
+  hipLaunchKernelGGL((attn_proj_kernel<QPK, HS, THROTTLE>),
+                     dim3(a.n_kv_heads + PB), dim3(256), smem, stream,
+                     (bf16*)a.out, (const bf16*)a.qkv, (bf16*)a.kpool,
+                     (bf16*)a.vpool, a.cos_t, a.sin_t, a.rope_ne, a.pos,
+                     a.slot, a.layer, a.n_layers_pool, a.n_kv_heads,
+                     a.max_seq, a.scale, (const bf16*)W, (const bf16*)bias,
+                     (const bf16*)res, (unsigned int*)gran, M, BR);
+}
+
+template <int QPK, int HS>
+static void launch_attn_proj_geom(const AttnArgs& a, const void* W,
+                                  const void* bias, const void* res,
+                                  void* gran, int M, hipStream_t stream) {
+  const int K = a.n_kv_heads * QPK * HS;
+  // rows per block group: fit every block resident at once (2 blocks/CU
+  // of 4 waves = the 8-wave/CU limit) AND the W tile in <=79 KB of LDS;
+  // grid-stride covers any remainder
+  // MDI_ATTN_PROJ_PB caps the number of proj (staging) blocks: fewer
+  // co-resident stagers leave the attention blocks' CUs unloaded (the
+  // "thin the loader while latency-sensitive work runs" principle,
+  // block-granular) at the cost of a longer-but-overlapped stage
+  static int pb_cap = -1;
+  if (pb_cap < 0) {
+    const char* e = getenv("MDI_ATTN_PROJ_PB");
+    pb_cap = e ? atoi(e) : 0;
+    if (pb_cap <= 0) pb_cap = 2 * 256;
+  }
+  const int cap_blocks =
+      (pb_cap < 2 * 256 ? pb_cap : 2 * 256) - a.n_kv_heads;
+  int BR = (M + cap_blocks - 1) / cap_blocks;
+  const int br_lds = (79 * 1024 - 16) / (K * 2);
+  if (br_lds < 1) return;  // K too large for the LDS tile (no instantiation)
+  if (BR > br_lds) BR = br_lds;
+  if (BR < 1) BR = 1;
+  int PB = (M + BR - 1) / BR;
+  if (PB > cap_blocks) PB = cap_blocks;
+  const size_t smem_proj = (size_t)BR * K * 2 + 16;  // +verdict word
+  const size_t smem_attn = AttnProjLds<QPK, HS>::total;
+  const size_t smem = smem_proj > smem_attn ? smem_proj : smem_attn;
+  static int thr = -1;
+  if (thr < 0) {
+    const char* e = getenv("MDI_ATTN_PROJ_SLEEP");
+    thr = e ? atoi(e) : 0;
+    if (thr != 0 && thr != 4 && thr != 8 && thr != 16) thr = 8;
+  }
+  auto with_thr = [&](auto t) {
+    constexpr int T = decltype(t)::value;
+    static bool attr_set = false;  // per (QPK, HS, T)
+    if (!attr_set) {
+      (void)hipFuncSetAttribute(
+          reinterpret_cast<const void*>(&attn_proj_kernel<QPK, HS, T>),
+          hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      attr_set = true;
+    }
+    launch_attn_proj_thr<QPK, HS, T>(a, W, bias, res, gran, M, BR, PB, smem,
+                                     stream);
+  };
+  if (thr == 0) with_thr(IC<0>{});
+  else if (thr == 4) with_thr(IC<4>{});
+  else if (thr == 8) with_thr(IC<8>{});
+  else with_thr(IC<16>{});
+}
+
+// fused attention+proj launcher.  Returns 0 on success, -1 when the
+// geometry has no instantiation (caller falls back to the split path).
+int launch_attn_proj(void* out, const void* qkv, void* kpool, void* vpool,
+                     const float* cos_t, const float* sin_t, int rope_ne,
+                     const int* pos, const int* slot, int layer,
+                     int n_layers_pool, int n_kv_heads, int max_seq,
+                     int head_size, int qpk, float scale, const void* W,
+                     const void* bias, const void* res, void* gran, int M,
+                     hipStream_t stream) {
+  if (max_seq > ATTN_BLOCK_MAX_SEQ) return -1;
+  const AttnArgs a{out, qkv, kpool, vpool, nullptr, nullptr, cos_t, sin_t,
+                   rope_ne, pos, slot, layer, n_layers_pool, n_kv_heads,
+                   max_seq, scale};
+  return attn_geom_dispatch(qpk, head_size, [&](auto q, auto h) {
+    launch_attn_proj_geom<decltype(q)::value, decltype(h)::value>(
+        a, W, bias, res, gran, M, stream);
+  });
 }
 
 void launch_rope_prefill_append(void* qkv, void* kpool, void* vpool,

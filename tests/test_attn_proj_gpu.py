@@ -59,6 +59,34 @@ def _i32(v):
     return torch.tensor(v, device=DEV, dtype=torch.int32)
 
 
+def proj_inputs(case, M, S):
+    """W, res, bias of one case (CPU, bf16)."""
+    K = case.n_head * case.hs
+    gen = torch.Generator().manual_seed(1000 + M + S)
+    W = (torch.randn(M, K, generator=gen) / math.sqrt(K)).to(torch.bfloat16)
+    res = torch.randn(M, generator=gen).to(torch.bfloat16)
+    bias = torch.randn(M, generator=gen).to(torch.bfloat16)
+    return W, res, bias
+
+
+def launch(ops, case, M, W, res, bias):
+    """Run attn_proj on device copies with a freshly zeroed scratch; bias
+    may be None.  Returns (guard-padded out buffer, kpool, vpool, qkv, cos,
+    sin, pos, slot), all on the device."""
+    K = case.n_head * case.hs
+    buf = torch.full((M + GUARD,), 12352.0, device=DEV, dtype=torch.bfloat16)
+    kpool, vpool = case.kpool.to(DEV), case.vpool.to(DEV)
+    qkv = case.qkv.to(DEV).reshape(-1).contiguous()
+    cos, sin = case.cos.to(DEV), case.sin.to(DEV)
+    pos, slot = _i32(case.pos), _i32(case.slot)
+    gran = torch.zeros(K // 2 + 16, device=DEV, dtype=torch.int32)
+    ops.attn_proj(buf[:M], qkv, kpool, vpool, cos, sin, pos, slot,
+                  case.layer, case.scale, W.to(DEV),
+                  None if bias is None else bias.to(DEV), res.to(DEV), gran)
+    torch.cuda.synchronize()
+    return buf, kpool, vpool, qkv, cos, sin, pos, slot
+
+
 @pytest.mark.parametrize(
     "geom,M,S,use_bias", PARAMS,
     ids=[f"q{g[0]}-kv{g[1]}-h{g[2]}-M{M}-S{S}-{'bias' if b else 'nobias'}"
@@ -68,11 +96,7 @@ def test_attn_proj(ops, geom, M, S, use_bias):
     ref = case.reference()
     assert case.probes_ok(ref), case.probe_weights(ref)
     K = case.n_head * case.hs
-
-    gen = torch.Generator().manual_seed(1000 + M + S)
-    W = (torch.randn(M, K, generator=gen) / math.sqrt(K)).to(torch.bfloat16)
-    res = torch.randn(M, generator=gen).to(torch.bfloat16)
-    bias = torch.randn(M, generator=gen).to(torch.bfloat16)
+    W, res, bias = proj_inputs(case, M, S)
 
     y = ref.out.reshape(K)
     A = ref.A.reshape(K)
@@ -84,17 +108,9 @@ def test_attn_proj(ops, geom, M, S, use_bias):
     tol = (2.0 ** -8 * want.abs() + 2.0 ** -9 * (Wd.abs() @ yb.abs())
            + Wd.abs() @ (2.0 ** -8 * y.abs() + 2.0 ** -9 * A))
 
-    buf = torch.full((M + GUARD,), 12352.0, device=DEV, dtype=torch.bfloat16)
-    tail = buf[M:].clone()
-    kpool, vpool = case.kpool.to(DEV), case.vpool.to(DEV)
-    qkv = case.qkv.to(DEV).reshape(-1).contiguous()
-    cos, sin = case.cos.to(DEV), case.sin.to(DEV)
-    pos, slot = _i32(case.pos), _i32(case.slot)
-    gran = torch.zeros(K // 2 + 16, device=DEV, dtype=torch.int32)
-    ops.attn_proj(buf[:M], qkv, kpool, vpool, cos, sin, pos, slot,
-                  case.layer, case.scale, W.to(DEV),
-                  bias.to(DEV) if use_bias else None, res.to(DEV), gran)
-    torch.cuda.synchronize()
+    tail = torch.full((GUARD,), 12352.0, device=DEV, dtype=torch.bfloat16)
+    buf, kpool, vpool, qkv, cos, sin, pos, slot = launch(
+        ops, case, M, W, res, bias if use_bias else None)
 
     got = buf[:M].cpu().double()
     err = (got - want).abs()

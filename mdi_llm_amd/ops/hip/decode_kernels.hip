@@ -3171,7 +3171,15 @@ __global__ void add_kernel(bf16* __restrict__ out, const bf16* __restrict__ a,
 //   [0..255]   hi-byte histogram
 //   [256..511] lo-byte histogram
 //   [512] bucket_hi, [513] count_above, [514] threshold_u16
-//   [516..517] packed (score,idx) u64 argmax cell (8-byte aligned)
+//   [515] largest sortable code (the max logit, for the mass phase)
+//   [516..517] packed (score,~idx) u64 argmax cell (8-byte aligned)
+//
+// Tie rule: on equal score the LOWEST index wins, at every level (thread,
+// wave, and the cross-wave atomicMax, which packs the complemented index).
+// The result therefore does not depend on the launch geometry (128 blocks
+// single-sample, 32 blocks batched), and greedy decoding (noise off) is
+// torch.argmax's first occurrence.  tests/sampler_reference.py is the
+// draw-for-draw CPU reference of the whole pipeline.
 // ---------------------------------------------------------------------------
 
 DEVINL unsigned bf16_sortable(unsigned short bits) {
@@ -3423,8 +3431,10 @@ __global__ void sample_gumbel_argmax_kernel(
   if ((threadIdx.x & 63) == 0) {
     unsigned sb = __float_as_uint(best);
     sb = (sb & 0x80000000u) ? ~sb : (sb | 0x80000000u);
+    // complemented index: on equal score the LOWER index wins the max,
+    // the same rule as inside a thread and inside a wave
     unsigned long long packed =
-        ((unsigned long long)sb << 32) | (unsigned)best_i;
+        ((unsigned long long)sb << 32) | ~(unsigned)best_i;
     atomicMax(reinterpret_cast<unsigned long long*>(&scratch[516]), packed);
   }
 }
@@ -3445,7 +3455,8 @@ __global__ void sample_unpack_kernel(unsigned* __restrict__ scratch,
   if (threadIdx.x == 0) {
     unsigned long long packed =
         *reinterpret_cast<const unsigned long long*>(&scratch[516]);
-    const int tok = (int)(unsigned)(packed & 0xFFFFFFFFull);
+    // the argmax kernel packs the complement of the index (tie rule)
+    const int tok = (int)~(unsigned)(packed & 0xFFFFFFFFull);
     out[0] = tok;
     if (slot) {
       const int sl = slot[0];

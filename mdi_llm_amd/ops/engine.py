@@ -13,7 +13,9 @@ Supported natively: RMSNorm/LayerNorm, rope/learned positions, GQA
 attention (head_size multiple of 32, head_size*q_per_kv >= 64), LLaMA
 (SwiGLU) / Gemma / GPT-NeoX MLPs, sequential and parallel residual.
 MoE decodes natively (device-side routing), also with fp8 expert slabs
-(the router weight stays bf16); int4+MoE is refused.
+(the router weight stays bf16); int4+MoE is refused.  MoE prompts prefill
+here too (moe_prefill_supported): device-side routing for any length, then
+the grouped decode kernels or expert-major library GEMMs.
 """
 
 from __future__ import annotations
@@ -27,7 +29,8 @@ from ..config import ModelConfig
 from ..models.model import KVCachePool
 from . import require_hip_ops
 
-__all__ = ["DecodeEngine", "engine_supported", "clamp_attn_chunks"]
+__all__ = ["DecodeEngine", "engine_supported", "clamp_attn_chunks",
+           "moe_prefill_supported", "hip_prefill_supported"]
 
 # attn_combine_kernel keeps chunk weights in 4 registers x 64 lanes
 ATTN_MAX_CHUNKS = 256
@@ -56,6 +59,42 @@ def engine_supported(config: ModelConfig) -> bool:
     if config.n_embd % 8 != 0 or (config.intermediate_size or 0) % 8 != 0:
         return False
     return True
+
+
+# moe_route_prefill lays out at most this many (token, rank) pairs a call
+MOE_PREFILL_MAX_PAIRS = 65536
+# the grouped expert kernels stage at most this many tokens
+MOE_GROUP_MAX_TOKENS = 128
+# Default of DecodeEngine.moe_prefill_group_max: prompts (chunks) of up to
+# this many tokens run the MoE MLP on the grouped decode kernels, longer
+# ones on expert-major library GEMMs.  Chosen from {0, 16, 32, 64, 128} by
+# the sweep of tools/bench_moe_prefill.py, recorded in
+# profiles/moe_prefill.md: 16 (measured on MI355X, Mixtral shapes: the
+# grouped path wins at T=16, 2.47 vs 3.50 ms, and loses from T=32 on).
+MOE_PREFILL_GROUP_MAX = 16
+
+
+def moe_prefill_supported(config: ModelConfig) -> bool:
+    """MoE configs whose prompt runs on the HIP prefill path."""
+    return (
+        config.mlp_class_name == "LLaMAMoE"
+        and config.norm_class_name == "RMSNorm"
+        and not config.parallel_residual
+        and config.n_embd % 32 == 0
+        and (config.intermediate_size or 0) % 32 == 0
+        and config.n_expert <= 64
+        and 1 <= config.n_expert_per_token <= min(8, config.n_expert)
+    )
+
+
+def hip_prefill_supported(config: ModelConfig) -> bool:
+    """Configs DecodeEngine.prefill_hidden runs; the rest prefill through
+    the torch stage forward."""
+    if config.mlp_class_name == "LLaMAMoE":
+        return moe_prefill_supported(config)
+    return (config.norm_class_name == "RMSNorm"
+            and config.mlp_class_name in ("LLaMAMLP", "GemmaMLP")
+            and not config.parallel_residual)
 
 
 def quantize_fp8_rowwise(w: torch.Tensor):
@@ -366,6 +405,9 @@ class DecodeEngine:
                                         dtype=torch.int32)
             self.moe_escale = torch.zeros(cfg.n_expert_per_token, device=dev,
                                           dtype=torch.float32)
+            # prefill: longest prompt (chunk) that runs the MoE MLP on the
+            # grouped decode kernels (those cap it at 128; 0: never)
+            self.moe_prefill_group_max = MOE_PREFILL_GROUP_MAX
         self.part_o = torch.zeros(
             n_head * n_chunks * hs, device=dev, dtype=torch.float32
         )
@@ -405,7 +447,7 @@ class DecodeEngine:
             warnings.warn(
                 f"MDI_KV_DTYPE=fp8 ignored for {cfg.name!r}: the fp8 KV "
                 "cache needs the HIP prefill path (RMSNorm + LLaMA/Gemma "
-                "MLP, sequential residual)"
+                "MLP or a supported MoE, sequential residual)"
             )
         if self.kv8:
             kv_pool.to_fp8()
@@ -717,10 +759,7 @@ class DecodeEngine:
     # ------------------------------------------------------------------
     @property
     def supports_hip_prefill(self) -> bool:
-        cfg = self.config
-        return (cfg.norm_class_name == "RMSNorm"
-                and cfg.mlp_class_name in ("LLaMAMLP", "GemmaMLP")
-                and not cfg.parallel_residual)
+        return hip_prefill_supported(self.config)
 
     @torch.inference_mode()
     def prefill_hidden(self, x: torch.Tensor, slot: int,
@@ -755,6 +794,9 @@ class DecodeEngine:
                 a = x + F.linear(Y, w.proj_w, w.proj_b)
             hn = xn
             ops.rmsnorm(hn, a, w.norm2_w, cfg.norm_eps)
+            if cfg.mlp_class_name == "LLaMAMoE":
+                x = self._moe_prefill_mlp(a, hn, w)
+                continue
             gelu_gate = cfg.mlp_class_name == "GemmaMLP"
             gate = F.linear(hn, w.fc1_w)
             up = F.linear(hn, w.fc2_w)
@@ -764,6 +806,94 @@ class DecodeEngine:
             else:
                 x = a + F.linear(up, w.mlp_proj_w, w.mlp_proj_b)
         return x
+
+    # MoE MLP half of the prefill.  Routing sees the bf16-rounded norm, as
+    # in the torch module; prefill reads the bf16 slabs under every
+    # MDI_WEIGHT_DTYPE.
+    def moe_prefill_route(self, hn: torch.Tensor, w: _BlockWeights) -> dict:
+        """Route the [T, n_embd] normed rows (T*k <= 65536): gate logits by
+        the library GEMM, then moe_route_prefill.  Returns eidx / escale /
+        count / offset / perm / inv in moe_route_group's layout."""
+        import torch.nn.functional as F
+
+        cfg = self.config
+        n_e, k = cfg.n_expert, cfg.n_expert_per_token
+        n = hn.size(0) * k
+        i32 = dict(device=self.device, dtype=torch.int32)
+        r = dict(
+            eidx=torch.empty(n, **i32),
+            escale=torch.empty(n, device=self.device, dtype=torch.float32),
+            count=torch.empty(n_e, **i32),
+            offset=torch.empty(n_e + 1, **i32),
+            perm=torch.empty(n, **i32),
+            inv=torch.empty(n, **i32),
+        )
+        logits = F.linear(hn, w.gate_w)
+        self.ops.moe_route_prefill(r["eidx"], r["escale"], r["count"],
+                                   r["offset"], r["perm"], r["inv"], logits,
+                                   k)
+        return r
+
+    def moe_prefill_experts(self, out: torch.Tensor, res: torch.Tensor,
+                            hn: torch.Tensor, w: _BlockWeights, r: dict,
+                            ACT: Optional[torch.Tensor] = None,
+                            D: Optional[torch.Tensor] = None) -> None:
+        """out[t] = res[t] + sum_rank escale * expert(hn[t]) on the routing
+        r (out may be res).  ACT [T*k, I] bf16 and D [T*k, n_embd] (fp32 on
+        the grouped path, bf16 on the expert-major one) are the permuted-row
+        buffers; rows that r maps nowhere are left untouched."""
+        cfg = self.config
+        ops = self.ops
+        k = cfg.n_expert_per_token
+        T, E = hn.shape
+        I = cfg.intermediate_size
+        n = T * k
+        bf = dict(device=self.device, dtype=torch.bfloat16)
+        if T <= min(self.moe_prefill_group_max, MOE_GROUP_MAX_TOKENS):
+            # short prompt: the decode group kernels, each touched expert
+            # streamed once, no host sync
+            if ACT is None:
+                ACT = torch.empty(n, I, **bf)
+            if D is None:
+                D = torch.empty(n, E, device=self.device,
+                                dtype=torch.float32)
+            ops.moe_group_swiglu(ACT, w.fc1_w, w.fc2_w, hn, r["count"],
+                                 r["offset"], r["perm"], r["escale"], k)
+            ops.moe_group_down(D, w.mlp_proj_w, ACT, r["count"],
+                               r["offset"], T)
+            ops.moe_group_combine(out, res, D, r["inv"], k)
+            return
+        # expert-major: one library GEMM per expert with rows, on the
+        # contiguous slice [offset[e], offset[e+1]) of the gathered rows.
+        # The slice bounds are the layer's one host sync.
+        XG = torch.empty(n, E, **bf)
+        ops.moe_prefill_gather(XG, hn, r["perm"], k)
+        G = torch.empty(n, I, **bf)
+        U = torch.empty(n, I, **bf)
+        if ACT is None:
+            ACT = U  # elementwise: act overwrites up in place
+        if D is None:
+            D = torch.empty(n, E, **bf)
+        off = r["offset"].cpu().tolist()
+        live = [(e, off[e], off[e + 1]) for e in range(cfg.n_expert)
+                if off[e + 1] > off[e]]
+        for e, lo, hi in live:
+            torch.mm(XG[lo:hi], w.fc1_w[e].t(), out=G[lo:hi])
+            torch.mm(XG[lo:hi], w.fc2_w[e].t(), out=U[lo:hi])
+        ops.moe_prefill_act(ACT, G, U, r["escale"], r["perm"])
+        for e, lo, hi in live:
+            torch.mm(ACT[lo:hi], w.mlp_proj_w[e].t(), out=D[lo:hi])
+        ops.moe_prefill_combine(out, res, D, r["inv"], k)
+
+    def _moe_prefill_mlp(self, a: torch.Tensor, hn: torch.Tensor,
+                         w: _BlockWeights) -> torch.Tensor:
+        """a += moe(hn), in chunks of tokens the router can lay out."""
+        cap = MOE_PREFILL_MAX_PAIRS // self.config.n_expert_per_token
+        for t0 in range(0, hn.size(0), cap):
+            h, a_c = hn[t0:t0 + cap], a[t0:t0 + cap]
+            self.moe_prefill_experts(a_c, a_c, h, w,
+                                     self.moe_prefill_route(h, w))
+        return a
 
     @torch.inference_mode()
     def prefill_prompt(self, tokens: torch.Tensor, slot: int,

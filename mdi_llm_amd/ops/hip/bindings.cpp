@@ -593,6 +593,91 @@ void moe_group_combine(torch::Tensor out, torch::Tensor res, torch::Tensor D,
                            (int)E, (int)k, cur_stream());
 }
 
+void moe_route_prefill(torch::Tensor eidx, torch::Tensor escale,
+                       torch::Tensor count, torch::Tensor offset,
+                       torch::Tensor perm, torch::Tensor inv,
+                       torch::Tensor logits, int64_t k) {
+  check_bf16(logits, "logits");
+  TORCH_CHECK(logits.dim() == 2 && logits.is_contiguous(),
+              "logits must be a contiguous [T, n_expert]");
+  const int64_t T = logits.size(0), n_e = logits.size(1);
+  TORCH_CHECK(T >= 1 && n_e >= 1 && n_e <= 64 && k >= 1 && k <= 8 &&
+                  k <= n_e && T * k <= 65536,
+              "moe_route_prefill: T*k <= 65536, n_e <= 64, "
+              "1 <= k <= min(8, n_e)");
+  check_i32n(eidx, "eidx", T * k);
+  check_f32(escale, "escale");
+  TORCH_CHECK(escale.is_contiguous() && escale.numel() == T * k,
+              "escale size");
+  check_i32n(count, "count", n_e);
+  check_i32n(offset, "offset", n_e + 1);
+  check_i32n(perm, "perm", T * k);
+  check_i32n(inv, "inv", T * k);
+  auto segcnt = torch::empty(
+      {(int64_t)moe_prefill_route_workspace((int)T, (int)n_e, (int)k)},
+      count.options());
+  const int rc = launch_moe_route_prefill(
+      eidx.data_ptr<int>(), escale.data_ptr<float>(), count.data_ptr<int>(),
+      offset.data_ptr<int>(), perm.data_ptr<int>(), inv.data_ptr<int>(),
+      segcnt.data_ptr<int>(), logits.data_ptr(), (int)T, (int)n_e, (int)k,
+      cur_stream());
+  TORCH_CHECK(rc == 0, "moe_route_prefill: size out of range");
+}
+
+inline void check_bf16_rows(const torch::Tensor& t, const char* name,
+                            int64_t rows, int64_t cols) {
+  check_bf16(t, name);
+  TORCH_CHECK(t.dim() == 2 && t.is_contiguous() && t.size(0) == rows &&
+                  t.size(1) == cols,
+              name, ": expected a contiguous [", rows, ", ", cols, "]");
+}
+
+void moe_prefill_gather(torch::Tensor XG, torch::Tensor hn,
+                        torch::Tensor perm, int64_t k) {
+  check_bf16(hn, "hn");
+  TORCH_CHECK(hn.dim() == 2 && hn.is_contiguous(), "hn must be [T, E]");
+  const int64_t T = hn.size(0), E = hn.size(1);
+  TORCH_CHECK(k >= 1 && T >= 1 && T * k <= 65536 && E % 8 == 0,
+              "moe_prefill_gather: T*k <= 65536, E % 8 == 0");
+  check_bf16_rows(XG, "XG", T * k, E);
+  check_i32n(perm, "perm", T * k);
+  launch_moe_prefill_gather(XG.data_ptr(), hn.data_ptr(),
+                            perm.data_ptr<int>(), (int)(T * k), (int)E,
+                            (int)k, cur_stream());
+}
+
+void moe_prefill_act(torch::Tensor ACT, torch::Tensor G, torch::Tensor U,
+                     torch::Tensor escale, torch::Tensor perm) {
+  check_bf16(G, "G");
+  TORCH_CHECK(G.dim() == 2 && G.is_contiguous(), "G must be [T*k, I]");
+  const int64_t R = G.size(0), I = G.size(1);
+  TORCH_CHECK(R >= 1 && R <= 65536 && I % 8 == 0,
+              "moe_prefill_act: T*k <= 65536, I % 8 == 0");
+  check_bf16_rows(U, "U", R, I);
+  check_bf16_rows(ACT, "ACT", R, I);
+  check_f32(escale, "escale");
+  TORCH_CHECK(escale.is_contiguous() && escale.numel() == R, "escale size");
+  check_i32n(perm, "perm", R);
+  launch_moe_prefill_act(ACT.data_ptr(), G.data_ptr(), U.data_ptr(),
+                         escale.data_ptr<float>(), perm.data_ptr<int>(),
+                         (int)R, (int)I, cur_stream());
+}
+
+void moe_prefill_combine(torch::Tensor out, torch::Tensor res,
+                         torch::Tensor D, torch::Tensor inv, int64_t k) {
+  check_bf16(res, "res");
+  TORCH_CHECK(res.dim() == 2 && res.is_contiguous(), "res must be [T, E]");
+  const int64_t T = res.size(0), E = res.size(1);
+  TORCH_CHECK(k >= 1 && T >= 1 && T * k <= 65536 && E % 8 == 0,
+              "moe_prefill_combine: T*k <= 65536, E % 8 == 0");
+  check_bf16_rows(out, "out", T, E);
+  check_bf16_rows(D, "D", T * k, E);
+  check_i32n(inv, "inv", T * k);
+  launch_moe_prefill_combine(out.data_ptr(), res.data_ptr(), D.data_ptr(),
+                             inv.data_ptr<int>(), (int)T, (int)E, (int)k,
+                             cur_stream());
+}
+
 void embed(torch::Tensor out, torch::Tensor wte, torch::Tensor token,
            double scale) {
   check_bf16(out, "out");
@@ -993,6 +1078,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("count"), py::arg("offset"), py::arg("n_tokens"));
   m.def("moe_group_combine", &moe_group_combine,
         "out[b] = res[b] + sum over ranks of the token's expert rows",
+        py::arg("out"), py::arg("res"), py::arg("D"), py::arg("inv"),
+        py::arg("k"));
+  m.def("moe_route_prefill", &moe_route_prefill,
+        "MoE prefill router: moe_route_group's outputs and layout for any "
+        "T with T*k <= 65536 (multi-block)",
+        py::arg("eidx"), py::arg("escale"), py::arg("count"),
+        py::arg("offset"), py::arg("perm"), py::arg("inv"),
+        py::arg("logits"), py::arg("k"));
+  m.def("moe_prefill_gather", &moe_prefill_gather,
+        "XG[s] = hn[perm[s] / k]",
+        py::arg("XG"), py::arg("hn"), py::arg("perm"), py::arg("k"));
+  m.def("moe_prefill_act", &moe_prefill_act,
+        "ACT[s] = silu(G[s]) * U[s] * escale[perm[s]], one bf16 rounding",
+        py::arg("ACT"), py::arg("G"), py::arg("U"), py::arg("escale"),
+        py::arg("perm"));
+  m.def("moe_prefill_combine", &moe_prefill_combine,
+        "out[t] = res[t] + sum over ranks of the token's bf16 expert rows",
         py::arg("out"), py::arg("res"), py::arg("D"), py::arg("inv"),
         py::arg("k"));
   m.def("embed", &embed, "embedding row gather");

@@ -105,6 +105,31 @@ void launch_moe_group_combine(void* out, const void* res, const float* D,
                               const int* inv, int Bsz, int E, int k,
                               hipStream_t stream);
 
+// MoE prefill router: the six outputs of launch_moe_route_group, same
+// layout, for any T >= 1 with T*k <= 65536 (multi-block, no atomics).
+// segcnt is scratch of moe_prefill_route_workspace(T, n_e, k) ints.
+// Returns -1 when T*k, n_e or k is out of range.
+int moe_prefill_route_workspace(int T, int n_e, int k);
+int launch_moe_route_prefill(int* eidx, float* escale, int* count,
+                             int* offset, int* perm, int* inv, int* segcnt,
+                             const void* logits, int T, int n_e, int k,
+                             hipStream_t stream);
+
+// row kernels of the expert-major prefill path (bf16, E % 8 == I % 8 == 0;
+// a row whose perm/inv entry is out of range is skipped):
+// XG[s] = hn[perm[s] / k]
+void launch_moe_prefill_gather(void* XG, const void* hn, const int* perm,
+                               int nrows, int E, int k, hipStream_t stream);
+// ACT[s] = bf16(silu(G[s]) * U[s] * escale[perm[s]])
+void launch_moe_prefill_act(void* ACT, const void* G, const void* U,
+                            const float* escale, const int* perm, int nrows,
+                            int I, hipStream_t stream);
+// out[t] = bf16(res[t] + sum_rank D[inv[t*k + rank]]), D bf16 (fp32 sum,
+// rank order; out may alias res)
+void launch_moe_prefill_combine(void* out, const void* res, const void* D,
+                                const int* inv, int T, int E, int k,
+                                hipStream_t stream);
+
 void launch_embed(void* out, const void* wte, const int* token, int n_embd,
                   float scale, hipStream_t stream);
 

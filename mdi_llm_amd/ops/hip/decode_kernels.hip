@@ -743,6 +743,53 @@ __global__ void moe_gate_topk_kernel(int* __restrict__ eidx,
 #define MOE_MAX_TOPK 8
 #define MOE_MAX_E 64
 
+// One token's routing, run by one full wave (lane = expert): top-k of the
+// row's gate logits, lowest index first among equals, then softmax over the
+// k selected logits.  Lane 0 writes eidx[0..k) / escale[0..k); every lane
+// returns the chosen experts in seli.  Shared by the decode group router and
+// the prefill router, so a prompt token and a decode token route alike.
+DEVINL void moe_token_topk(int* __restrict__ eidx, float* __restrict__ escale,
+                           const bf16* __restrict__ row, int n_e, int k,
+                           int lane, int (&seli)[MOE_MAX_TOPK]) {
+  float cur = (lane < n_e) ? b2f(row[lane]) : -1e30f;
+  float selv[MOE_MAX_TOPK];
+#pragma unroll
+  for (int j = 0; j < MOE_MAX_TOPK; ++j) {
+    if (j >= k) continue;
+    float m = cur;
+    int mi = lane;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const float om = __shfl_xor(m, off, 64);
+      const int oi = __shfl_xor(mi, off, 64);
+      if (om > m || (om == m && oi < mi)) {
+        m = om;
+        mi = oi;
+      }
+    }
+    selv[j] = m;
+    seli[j] = mi;
+    if (lane == mi) cur = -1e30f;
+  }
+  if (lane == 0) {
+    const float mx = selv[0];
+    float ssum = 0.f;
+    float ex[MOE_MAX_TOPK];
+#pragma unroll
+    for (int j = 0; j < MOE_MAX_TOPK; ++j) {
+      ex[j] = (j < k) ? __expf(selv[j] - mx) : 0.f;
+      ssum += ex[j];
+    }
+#pragma unroll
+    for (int j = 0; j < MOE_MAX_TOPK; ++j) {
+      if (j < k) {
+        eidx[j] = seli[j];
+        escale[j] = ex[j] / ssum;
+      }
+    }
+  }
+}
+
 __global__ __launch_bounds__(1024) void moe_route_group_kernel(
     int* __restrict__ eidx, float* __restrict__ escale,
     int* __restrict__ count, int* __restrict__ offset,
@@ -757,44 +804,13 @@ __global__ __launch_bounds__(1024) void moe_route_group_kernel(
 
   // ---- per-token top-k + softmax: one wave per token, lane = expert ----
   for (int b = wave; b < B; b += nw) {
-    float cur = (lane < n_e) ? b2f(logits[b * n_e + lane]) : -1e30f;
-    float selv[MOE_MAX_TOPK];
     int seli[MOE_MAX_TOPK];
-#pragma unroll
-    for (int j = 0; j < MOE_MAX_TOPK; ++j) {
-      if (j >= k) continue;
-      float m = cur;
-      int mi = lane;
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) {
-        const float om = __shfl_xor(m, off, 64);
-        const int oi = __shfl_xor(mi, off, 64);
-        if (om > m || (om == m && oi < mi)) {
-          m = om;
-          mi = oi;
-        }
-      }
-      selv[j] = m;
-      seli[j] = mi;
-      if (lane == mi) cur = -1e30f;
-    }
+    moe_token_topk(eidx + b * k, escale + b * k, logits + b * n_e, n_e, k,
+                   lane, seli);
     if (lane == 0) {
-      const float mx = selv[0];
-      float ssum = 0.f;
-      float ex[MOE_MAX_TOPK];
 #pragma unroll
-      for (int j = 0; j < MOE_MAX_TOPK; ++j) {
-        ex[j] = (j < k) ? __expf(selv[j] - mx) : 0.f;
-        ssum += ex[j];
-      }
-#pragma unroll
-      for (int j = 0; j < MOE_MAX_TOPK; ++j) {
-        if (j < k) {
-          eidx[b * k + j] = seli[j];
-          escale[b * k + j] = ex[j] / ssum;
-          sel[b * k + j] = seli[j];
-        }
-      }
+      for (int j = 0; j < MOE_MAX_TOPK; ++j)
+        if (j < k) sel[b * k + j] = seli[j];
     }
   }
   __syncthreads();
@@ -1140,6 +1156,182 @@ __global__ void moe_group_combine_kernel(bf16* __restrict__ out,
 #pragma unroll
   for (int j = 0; j < 8; ++j) o.v[j] = f2b(acc[j]);
   *reinterpret_cast<int4*>(out + (size_t)b * E + i) =
+      *reinterpret_cast<const int4*>(o.v);
+}
+
+// ---------------------------------------------------------------------------
+// MoE prefill: the same routing and row layout for a prompt of any length
+// T with T*k <= MOE_PREFILL_MAX_PAIRS, multi-block.  The expert GEMMs of a
+// long prompt are library GEMMs on contiguous expert-major slices, so the
+// kernels here only route, gather, activate and combine rows.
+//
+// Router, four launches, no atomics (perm is a pure function of the logits):
+//   topk    one wave per token (moe_token_topk), eidx/escale to global
+//   count   wave (e, seg): hits of expert e among the MOE_SEG pairs of
+//           segment seg, ballot + popcount -> segcnt[e, seg]
+//   prefix  one block: count[e], offset[e], and segcnt[e, seg] becomes the
+//           first row of (e, seg)
+//   scatter wave (e, seg) walks its segment again in ascending f and writes
+//           perm/inv from that base
+// ---------------------------------------------------------------------------
+#define MOE_PREFILL_MAX_PAIRS 65536
+#define MOE_SEG 1024
+
+__global__ __launch_bounds__(256) void moe_prefill_topk_kernel(
+    int* __restrict__ eidx, float* __restrict__ escale,
+    const bf16* __restrict__ logits, int T, int n_e, int k) {
+  const int lane = threadIdx.x & 63;
+  const int t = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
+  if (t >= T) return;  // wave-uniform
+  int seli[MOE_MAX_TOPK];
+  moe_token_topk(eidx + (size_t)t * k, escale + (size_t)t * k,
+                 logits + (size_t)t * n_e, n_e, k, lane, seli);
+}
+
+// grid (nseg, ceil(n_e / 4)), 4 waves: wave w owns expert blockIdx.y*4 + w
+__global__ __launch_bounds__(256) void moe_prefill_count_kernel(
+    int* __restrict__ segcnt, const int* __restrict__ eidx, int n, int n_e,
+    int nseg) {
+  const int lane = threadIdx.x & 63;
+  const int e = (int)blockIdx.y * 4 + ((int)threadIdx.x >> 6);
+  const int seg = blockIdx.x;
+  if (e >= n_e) return;
+  const int f_end = min(n, (seg + 1) * MOE_SEG);
+  int c = 0;
+  for (int f0 = seg * MOE_SEG; f0 < f_end; f0 += 64) {
+    const int f = f0 + lane;
+    const bool hit = f < f_end && eidx[f] == e;
+    c += __popcll(__ballot(hit));
+  }
+  if (lane == 0) segcnt[e * nseg + seg] = c;
+}
+
+// one block of 64 threads, thread = expert
+__global__ __launch_bounds__(64) void moe_prefill_prefix_kernel(
+    int* __restrict__ count, int* __restrict__ offset,
+    int* __restrict__ segcnt, int n_e, int nseg) {
+  __shared__ int cnt_s[MOE_MAX_E];
+  __shared__ int off_s[MOE_MAX_E + 1];
+  const int e = threadIdx.x;
+  if (e < n_e) {
+    int c = 0;
+    for (int sg = 0; sg < nseg; ++sg) c += segcnt[e * nseg + sg];
+    cnt_s[e] = c;
+    count[e] = c;
+  }
+  __syncthreads();
+  if (e == 0) {
+    int run = 0;
+    for (int x = 0; x < n_e; ++x) {
+      off_s[x] = run;
+      run += cnt_s[x];
+    }
+    off_s[n_e] = run;
+  }
+  __syncthreads();
+  if (e < n_e) offset[e] = off_s[e];
+  if (e == 0) offset[n_e] = off_s[n_e];
+  if (e < n_e) {
+    int run = off_s[e];
+    for (int sg = 0; sg < nseg; ++sg) {
+      const int c = segcnt[e * nseg + sg];
+      segcnt[e * nseg + sg] = run;
+      run += c;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void moe_prefill_scatter_kernel(
+    int* __restrict__ perm, int* __restrict__ inv,
+    const int* __restrict__ segbase, const int* __restrict__ eidx, int n,
+    int n_e, int nseg) {
+  const int lane = threadIdx.x & 63;
+  const int e = (int)blockIdx.y * 4 + ((int)threadIdx.x >> 6);
+  const int seg = blockIdx.x;
+  if (e >= n_e) return;
+  const int f_end = min(n, (seg + 1) * MOE_SEG);
+  int run = segbase[e * nseg + seg];
+  for (int f0 = seg * MOE_SEG; f0 < f_end; f0 += 64) {
+    const int f = f0 + lane;
+    const bool hit = f < f_end && eidx[f] == e;
+    const unsigned long long mask = __ballot(hit);
+    if (hit) {
+      const int s = run + __popcll(mask & ((1ull << lane) - 1ull));
+      if (s >= 0 && s < n) {
+        perm[s] = f;
+        inv[f] = s;
+      }
+    }
+    run += __popcll(mask);
+  }
+}
+
+// Row kernels of the expert-major prefill path: block x = row, block y
+// covers the row 2048 elements at a time, 16 B per lane.  A row whose map
+// entry is out of range is left untouched.
+
+// XG[s] = hn[perm[s] / k]
+__global__ __launch_bounds__(256) void moe_prefill_gather_kernel(
+    bf16* __restrict__ XG, const bf16* __restrict__ hn,
+    const int* __restrict__ perm, int E, int k, int nrows) {
+  const int s = blockIdx.x;
+  const int i = ((int)blockIdx.y * 256 + (int)threadIdx.x) * 8;
+  if (i >= E) return;
+  const int f = perm[s];
+  if (f < 0 || f >= nrows) return;
+  *reinterpret_cast<int4*>(XG + (size_t)s * E + i) =
+      *reinterpret_cast<const int4*>(hn + (size_t)(f / k) * E + i);
+}
+
+// ACT[s] = bf16(silu(G[s]) * U[s] * escale[perm[s]]): fp32, one rounding,
+// the routing weight before it (as moe_group_gemm_kernel)
+__global__ __launch_bounds__(256) void moe_prefill_act_kernel(
+    bf16* __restrict__ ACT, const bf16* __restrict__ G,
+    const bf16* __restrict__ U, const float* __restrict__ escale,
+    const int* __restrict__ perm, int I, int nrows) {
+  const int s = blockIdx.x;
+  const int i = ((int)blockIdx.y * 256 + (int)threadIdx.x) * 8;
+  if (i >= I) return;
+  const int f = perm[s];
+  if (f < 0 || f >= nrows) return;
+  const float sc = escale[f];
+  const bf16x8 gv = load8(G + (size_t)s * I + i);
+  const bf16x8 uv = load8(U + (size_t)s * I + i);
+  bf16x8 o;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const float a = b2f(gv.v[j]);
+    const float act = a / (1.f + expf(-a));
+    o.v[j] = f2b(act * b2f(uv.v[j]) * sc);
+  }
+  *reinterpret_cast<int4*>(ACT + (size_t)s * I + i) =
+      *reinterpret_cast<const int4*>(o.v);
+}
+
+// out[t] = bf16(res[t] + sum_rank D[inv[t*k + rank]]), D bf16: the twin of
+// moe_group_combine_kernel (fp32 sum, ranks 0..k-1, out may alias res)
+__global__ __launch_bounds__(256) void moe_prefill_combine_kernel(
+    bf16* __restrict__ out, const bf16* __restrict__ res,
+    const bf16* __restrict__ D, const int* __restrict__ inv, int E, int k,
+    int nrows) {
+  const int t = blockIdx.x;
+  const int i = ((int)blockIdx.y * 256 + (int)threadIdx.x) * 8;
+  if (i >= E) return;
+  const bf16x8 rv = load8(res + (size_t)t * E + i);
+  float acc[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc[j] = b2f(rv.v[j]);
+  for (int rk = 0; rk < k; ++rk) {
+    const int s = inv[t * k + rk];
+    if (s < 0 || s >= nrows) continue;
+    const bf16x8 dv = load8(D + (size_t)s * E + i);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] += b2f(dv.v[j]);
+  }
+  bf16x8 o;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) o.v[j] = f2b(acc[j]);
+  *reinterpret_cast<int4*>(out + (size_t)t * E + i) =
       *reinterpret_cast<const int4*>(o.v);
 }
 
@@ -3919,6 +4111,57 @@ void launch_moe_group_combine(void* out, const void* res, const float* D,
   const dim3 grid((E / 8 + 255) / 256, Bsz);
   hipLaunchKernelGGL(moe_group_combine_kernel, grid, dim3(256), 0, stream,
                      (bf16*)out, (const bf16*)res, D, inv, E, k, Bsz * k);
+}
+
+int moe_prefill_route_workspace(int T, int n_e, int k) {
+  const int nseg = (T * k + MOE_SEG - 1) / MOE_SEG;
+  return n_e * nseg;
+}
+
+int launch_moe_route_prefill(int* eidx, float* escale, int* count,
+                             int* offset, int* perm, int* inv, int* segcnt,
+                             const void* logits, int T, int n_e, int k,
+                             hipStream_t stream) {
+  if (T < 1 || n_e < 1 || n_e > MOE_MAX_E || k < 1 || k > MOE_MAX_TOPK ||
+      k > n_e || (long long)T * k > MOE_PREFILL_MAX_PAIRS)
+    return -1;
+  const int n = T * k;
+  const int nseg = (n + MOE_SEG - 1) / MOE_SEG;
+  const dim3 grid(nseg, (n_e + 3) / 4);
+  hipLaunchKernelGGL(moe_prefill_topk_kernel, dim3((T + 3) / 4), dim3(256), 0,
+                     stream, eidx, escale, (const bf16*)logits, T, n_e, k);
+  hipLaunchKernelGGL(moe_prefill_count_kernel, grid, dim3(256), 0, stream,
+                     segcnt, eidx, n, n_e, nseg);
+  hipLaunchKernelGGL(moe_prefill_prefix_kernel, dim3(1), dim3(64), 0, stream,
+                     count, offset, segcnt, n_e, nseg);
+  hipLaunchKernelGGL(moe_prefill_scatter_kernel, grid, dim3(256), 0, stream,
+                     perm, inv, segcnt, eidx, n, n_e, nseg);
+  return 0;
+}
+
+void launch_moe_prefill_gather(void* XG, const void* hn, const int* perm,
+                               int nrows, int E, int k, hipStream_t stream) {
+  const dim3 grid(nrows, (E / 8 + 255) / 256);
+  hipLaunchKernelGGL(moe_prefill_gather_kernel, grid, dim3(256), 0, stream,
+                     (bf16*)XG, (const bf16*)hn, perm, E, k, nrows);
+}
+
+void launch_moe_prefill_act(void* ACT, const void* G, const void* U,
+                            const float* escale, const int* perm, int nrows,
+                            int I, hipStream_t stream) {
+  const dim3 grid(nrows, (I / 8 + 255) / 256);
+  hipLaunchKernelGGL(moe_prefill_act_kernel, grid, dim3(256), 0, stream,
+                     (bf16*)ACT, (const bf16*)G, (const bf16*)U, escale, perm,
+                     I, nrows);
+}
+
+void launch_moe_prefill_combine(void* out, const void* res, const void* D,
+                                const int* inv, int T, int E, int k,
+                                hipStream_t stream) {
+  const dim3 grid(T, (E / 8 + 255) / 256);
+  hipLaunchKernelGGL(moe_prefill_combine_kernel, grid, dim3(256), 0, stream,
+                     (bf16*)out, (const bf16*)res, (const bf16*)D, inv, E, k,
+                     T * k);
 }
 
 void launch_embed(void* out, const void* wte, const int* token, int n_embd,

@@ -4,6 +4,12 @@ moe_group_down), the rank-ordered combine, and GroupDecodeEngine on
 LLaMAMoE stages (graph vs eager, logits vs the torch GPT with the
 single-sample DecodeEngine as yardstick, mid-stage engine).
 
+The kernel cases here are sized for nano-moe-gpu (K <= 512): at RB <= 64
+they run one K-chunk, so the weight ring refill, the X double buffer and
+ragged last chunks are NOT covered here, nor are tied logits (every router
+test asserts tie-free input).  tests/test_moe_matrix_gpu.py covers those
+against the fp64 references of tests/moe_reference.py.
+
 Layout convention under test: the B*k (token, rank) pairs are numbered
 f = token*k + rank; permuted row s in [offset[e], offset[e+1]) belongs to
 expert e and holds pair perm[s], ascending in f inside an expert;
@@ -221,6 +227,7 @@ GEMM_CASES = [
     (256, 224, 4, 2, 16, "random"),
     (256, 224, 4, 2, 17, "random"),
     (256, 224, 4, 2, 33, "random"),
+    (256, 224, 4, 2, 128, "random"),     # RB=128
     (512, 64, 8, 2, 5, "random"),
     (256, 224, 4, 2, 33, "same_two"),    # counts 33: three tiles, ragged
     (256, 224, 4, 2, 17, "starved"),     # one expert with count 0

@@ -10,7 +10,8 @@ which sample is flowing through (reference swaps per-sample cache objects
 into the modules instead — gptserver.py:975-978).
 
 Supported natively: RMSNorm/LayerNorm, rope/learned positions, GQA
-attention (head_size multiple of 32, head_size*q_per_kv >= 64), LLaMA
+attention (head_size 64, 128 or 256 with q_per_kv in 1, 2, 4, 8, 16) and
+MHA with head_size 80 (phi-2, StableLM-3B, Pythia-2.8B), LLaMA
 (SwiGLU) / Gemma / GPT-NeoX MLPs, sequential and parallel residual.
 MoE decodes natively (device-side routing), also with fp8 expert slabs
 (the router weight stays bf16); int4+MoE is refused.  MoE prompts prefill
@@ -49,9 +50,9 @@ def engine_supported(config: ModelConfig) -> bool:
         or config.norm_class_name != "RMSNorm"
     ):
         return False
-    if config.head_size % 32 != 0 or config.head_size * config.q_per_kv < 64:
-        return False
-    if config.head_size not in (64, 128, 256):
+    # head size 80 has MHA kernels of its own (attn_mha_kernels.hip)
+    mha80 = config.head_size == 80 and config.q_per_kv == 1
+    if not mha80 and config.head_size not in (64, 128, 256):
         return False
     if config.q_per_kv not in (1, 2, 4, 8, 16):
         return False  # attention kernel instantiations (e.g. falcon-7b's
@@ -465,6 +466,7 @@ class DecodeEngine:
             and not self.int4
             and not self.kv8
             and not cfg.parallel_residual
+            and cfg.head_size in (64, 128, 256)
             and stage.max_seq_length <= 4096
             and K_attn % 128 == 0
             and K_attn // 2 <= 4096

@@ -154,6 +154,27 @@ int launch_attn_decode(void* out, float* part_o, float* part_ml,
                        int head_size, int qpk, int n_chunks, float scale,
                        int n_batch, int force_split, hipStream_t stream);
 
+// arguments every decode-attention launch forwards to its kernel
+struct AttnArgs {
+  void* out;
+  const void* qkv;
+  void *kpool, *vpool;
+  float *kscale, *vscale;  // fp8 KV row scales, or null for bf16 KV
+  const float *cos_t, *sin_t;
+  int rope_ne;
+  const int *pos, *slot;
+  int layer, n_layers_pool, n_kv_heads, max_seq;
+  float scale;
+};
+
+// q_per_kv == 1, head_size == 80 (attn_mha_kernels.hip); n_kv_heads is
+// the head count.  split: one wave per (head, chunk) writes part_o/part_ml
+// in the layout attn_combine_kernel reads (the caller launches it); else
+// one block per (sample, head) writes out.  n_batch as above.
+void launch_attn_mha80(const AttnArgs& a, float* part_o, float* part_ml,
+                       int n_chunks, int n_batch, bool split,
+                       hipStream_t stream);
+
 void launch_add(void* out, const void* a, const void* b, int n,
                 hipStream_t stream);
 

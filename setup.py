@@ -28,19 +28,25 @@ ROCM_HOME = os.environ.get("ROCM_HOME", os.environ.get("ROCM_PATH", "/opt/rocm")
 HIPCC = os.path.join(ROCM_HOME, "bin", "hipcc")
 OFFLOAD_ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950").split(";")[0]
 
-KERNEL_SOURCES = ["decode_kernels.hip"]
+# kernel TU -> extra hipcc flags.  attn_mha_kernels.hip is built without
+# the packed fp32 instruction forms (its loops scale fp32 rows by a scalar).
+NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+KERNEL_SOURCES = {
+    "decode_kernels.hip": [],
+    "attn_mha_kernels.hip": NO_PACKED_FP32,
+}
+KERNEL_HEADERS = ["decode_kernels.h", "device_common.h"]
 
 
 def compile_hip_objects() -> list:
     BUILD_DIR.mkdir(parents=True, exist_ok=True)
     objs = []
-    for src in KERNEL_SOURCES:
+    for src, extra in KERNEL_SOURCES.items():
         src_path = HIP_DIR / src
         obj_path = BUILD_DIR / (src_path.stem + ".o")
-        if (
-            not obj_path.exists()
-            or obj_path.stat().st_mtime < src_path.stat().st_mtime
-            or obj_path.stat().st_mtime < (HIP_DIR / "decode_kernels.h").stat().st_mtime
+        deps = [src_path] + [HIP_DIR / h for h in KERNEL_HEADERS]
+        if not obj_path.exists() or any(
+            obj_path.stat().st_mtime < d.stat().st_mtime for d in deps
         ):
             cmd = [
                 HIPCC,
@@ -48,6 +54,7 @@ def compile_hip_objects() -> list:
                 "-O3",
                 "-std=c++17",
                 "-fPIC",
+                *extra,
                 "-c",
                 str(src_path),
                 "-o",

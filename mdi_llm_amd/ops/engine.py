@@ -14,9 +14,16 @@ attention (head_size 64, 128 or 256 with q_per_kv in 1, 2, 4, 8, 16) and
 MHA with head_size 80 (phi-2, StableLM-3B, Pythia-2.8B), LLaMA
 (SwiGLU) / Gemma / GPT-NeoX MLPs, sequential and parallel residual.
 MoE decodes natively (device-side routing), also with fp8 expert slabs
-(the router weight stays bf16); int4+MoE is refused.  MoE prompts prefill
-here too (moe_prefill_supported): device-side routing for any length, then
-the grouped decode kernels or expert-major library GEMMs.
+(the router weight stays bf16); int4+MoE is refused.
+
+Prompts prefill here as well (hip_prefill_supported): library GEMMs around
+the hand-written rope-append and causal flash attention, for every dense
+block form above (LayerNorm with bias, parallel residual with or without a
+shared norm, GptNeoxMLP, partial / no rotary, learned positions) at head
+size 64, 128 or 256, or 80 with q_per_kv 1.  That is also what lets the fp8
+KV cache (MDI_KV_DTYPE=fp8) turn on for a config.  MoE prompts
+(moe_prefill_supported): device-side routing for any length, then the
+grouped decode kernels or expert-major library GEMMs.
 """
 
 from __future__ import annotations
@@ -93,9 +100,11 @@ def hip_prefill_supported(config: ModelConfig) -> bool:
     the torch stage forward."""
     if config.mlp_class_name == "LLaMAMoE":
         return moe_prefill_supported(config)
-    return (config.norm_class_name == "RMSNorm"
-            and config.mlp_class_name in ("LLaMAMLP", "GemmaMLP")
-            and not config.parallel_residual)
+    # dense: every norm / MLP / residual form the engine decodes, at the
+    # head geometries prefill_attn has a kernel for
+    return engine_supported(config) and (
+        config.head_size in (64, 128, 256)
+        or (config.head_size == 80 and config.q_per_kv == 1))
 
 
 def quantize_fp8_rowwise(w: torch.Tensor):
@@ -447,8 +456,9 @@ class DecodeEngine:
 
             warnings.warn(
                 f"MDI_KV_DTYPE=fp8 ignored for {cfg.name!r}: the fp8 KV "
-                "cache needs the HIP prefill path (RMSNorm + LLaMA/Gemma "
-                "MLP or a supported MoE, sequential residual)"
+                "cache needs the HIP prefill path (head size 64, 128 or "
+                "256, or 80 with q_per_kv 1; for MoE see "
+                "moe_prefill_supported)"
             )
         if self.kv8:
             kv_pool.to_fp8()
@@ -777,8 +787,14 @@ class DecodeEngine:
         Y = torch.empty(T, cfg.n_head * cfg.head_size, device=self.device,
                         dtype=torch.bfloat16)
         xn = torch.empty_like(x)
+        if cfg.norm_class_name == "RMSNorm":
+            def norm(out, src, nw, nb):
+                ops.rmsnorm(out, src, nw, cfg.norm_eps)
+        else:
+            def norm(out, src, nw, nb):
+                ops.layernorm(out, src, nw, nb, cfg.norm_eps)
         for li, w in enumerate(self.blocks):
-            ops.rmsnorm(xn, x, w.norm1_w, cfg.norm_eps)
+            norm(xn, x, w.norm1_w, w.norm1_b)
             qkv = F.linear(xn, w.attn_w, w.attn_b)
             ops.rope_prefill_append(qkv, self.kv_pool.k, self.kv_pool.v,
                                     self.cos, self.sin, pos0, slot, li,
@@ -794,15 +810,26 @@ class DecodeEngine:
                 a = torch.addmm(x, Y, w.proj_w.t())
             else:
                 a = x + F.linear(Y, w.proj_w, w.proj_b)
+            # the MLP reads norm_2 of a (sequential) or of x (parallel: x +
+            # attn(n1) + mlp(n2), so a doubles as the MLP's residual); xn is
+            # free again once qkv is out, and under shared_attention_norm
+            # it already holds n2
             hn = xn
-            ops.rmsnorm(hn, a, w.norm2_w, cfg.norm_eps)
+            if not cfg.parallel_residual:
+                norm(hn, a, w.norm2_w, w.norm2_b)
+            elif not cfg.shared_attention_norm:
+                norm(hn, x, w.norm2_w, w.norm2_b)
             if cfg.mlp_class_name == "LLaMAMoE":
                 x = self._moe_prefill_mlp(a, hn, w)
                 continue
-            gelu_gate = cfg.mlp_class_name == "GemmaMLP"
-            gate = F.linear(hn, w.fc1_w)
-            up = F.linear(hn, w.fc2_w)
-            ops.swiglu_mul(up, gate, up, gelu_gate)
+            if cfg.mlp_class_name == "GptNeoxMLP":
+                up = F.linear(hn, w.fc_w, w.fc_b)
+                torch._C._nn.gelu_(up, approximate=cfg.gelu_approximate)
+            else:
+                gelu_gate = cfg.mlp_class_name == "GemmaMLP"
+                gate = F.linear(hn, w.fc1_w)
+                up = F.linear(hn, w.fc2_w)
+                ops.swiglu_mul(up, gate, up, gelu_gate)
             if w.mlp_proj_b is None:
                 x = torch.addmm(a, up, w.mlp_proj_w.t())
             else:
@@ -906,6 +933,8 @@ class DecodeEngine:
         x = F.embedding(tokens.long().view(-1), self.wte)
         if self.config.scale_embeddings:
             x = x * (self.config.n_embd ** 0.5)
+        if self.wpe is not None:
+            x = x + self.wpe[pos0:pos0 + x.size(0)]
         return self.prefill_hidden(x, slot, pos0)
 
     # ------------------------------------------------------------------

@@ -181,13 +181,15 @@ void layernorm(torch::Tensor out, torch::Tensor x, torch::Tensor w,
   check_bf16(out, "out");
   check_bf16(x, "x");
   check_bf16(w, "w");
-  const int n = (int)x.numel();
-  TORCH_CHECK(n > 0, "empty layernorm");
+  const int n = (int)w.numel();
+  TORCH_CHECK(n > 0 && x.numel() > 0, "empty layernorm");
+  const int nb = (int)(x.numel() / n);
   TORCH_CHECK(n % 8 == 0, "n must be a multiple of 8");
-  TORCH_CHECK(w.numel() == n && out.numel() == n, "size mismatch");
+  TORCH_CHECK(x.numel() == (int64_t)nb * n && out.numel() == x.numel(),
+              "size mismatch");
   const void* bp = opt_bf16_vec(b, n, "b");
   launch_layernorm(out.data_ptr(), x.data_ptr(), w.data_ptr(), bp, n,
-                   (float)eps, cur_stream());
+                   (float)eps, nb, cur_stream());
 }
 
 void gemv(torch::Tensor out, torch::Tensor W, torch::Tensor x,
@@ -1001,7 +1003,7 @@ void add(torch::Tensor out, torch::Tensor a, torch::Tensor b) {
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "mdi_llm_amd hand-written CDNA4 (gfx950) decode kernels";
   m.def("rmsnorm", &rmsnorm, "RMSNorm (decode, bf16)");
-  m.def("layernorm", &layernorm, "LayerNorm (decode, bf16)");
+  m.def("layernorm", &layernorm, "LayerNorm over rows of [B, n] (bf16)");
   m.def("gemv", &gemv, "decode GEMV out = W@norm?(x) (+bias)(+res)(act)",
         py::arg("out"), py::arg("W"), py::arg("x"), py::arg("bias"),
         py::arg("res"), py::arg("epilogue"),

@@ -10,7 +10,7 @@ void launch_rmsnorm(void* out, const void* x, const void* w, int n, float eps,
                     int n_batch, hipStream_t stream);
 
 void launch_layernorm(void* out, const void* x, const void* w, const void* b,
-                      int n, float eps, hipStream_t stream);
+                      int n, float eps, int n_batch, hipStream_t stream);
 
 // epilogue: 0 none, 1 +res, 2 gelu(tanh), 3 silu
 // norm_kind: 0 none, 1 fused RMSNorm on x, 2 fused LayerNorm on x
@@ -175,6 +175,16 @@ void launch_attn_mha80(const AttnArgs& a, float* part_o, float* part_ml,
                        int n_chunks, int n_batch, bool split,
                        hipStream_t stream);
 
+// prefill attention for q_per_kv == 1, head_size == 80
+// (attn_mha_kernels.hip); launch_prefill_attn dispatches to it.  Arguments
+// as launch_prefill_attn's, n_head is the (kv) head count.
+void launch_prefill_attn_mha80(void* out, const void* qkv, const void* kpool,
+                               const void* vpool, const float* kscale,
+                               const float* vscale, int pos0, int slot,
+                               int layer, int n_layers_pool, int n_head,
+                               int max_seq, int T, float scale,
+                               hipStream_t stream);
+
 void launch_add(void* out, const void* a, const void* b, int n,
                 hipStream_t stream);
 
@@ -229,7 +239,8 @@ void launch_rope_prefill_append(void* qkv, void* kpool, void* vpool,
                                 int max_seq, int head_size, int rope_ne,
                                 int qpk, int T, hipStream_t stream);
 
-// prefill flash attention (causal, GQA); out [T, n_head*head_size]
+// prefill flash attention (causal, GQA); out [T, n_head*head_size].
+// head_size 64, 128, 256 at any qpk, head_size 80 at qpk 1; else -1
 int launch_prefill_attn(void* out, const void* qkv, const void* kpool,
                         const void* vpool, const float* kscale,
                         const float* vscale, int pos0, int slot, int layer,

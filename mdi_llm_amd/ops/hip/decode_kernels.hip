@@ -65,7 +65,7 @@ __global__ void rmsnorm_kernel(bf16* __restrict__ out,
 }
 
 // ---------------------------------------------------------------------------
-// LayerNorm (decode): out = (x-mean)/sqrt(var+eps) * w + b
+// LayerNorm: out = (x-mean)/sqrt(var+eps) * w + b
 // ---------------------------------------------------------------------------
 __global__ void layernorm_kernel(bf16* __restrict__ out,
                                  const bf16* __restrict__ x,
@@ -73,6 +73,9 @@ __global__ void layernorm_kernel(bf16* __restrict__ out,
                                  const bf16* __restrict__ b, int n,
                                  float eps) {
   __shared__ float red[8];
+  // batched: row blockIdx.y of [B, n]
+  out += (size_t)blockIdx.y * n;
+  x += (size_t)blockIdx.y * n;
   const int tid = threadIdx.x;
   float s = 0.f, s2 = 0.f;
   for (int i = tid * 8; i < n; i += blockDim.x * 8) {
@@ -3666,10 +3669,10 @@ void launch_rmsnorm(void* out, const void* x, const void* w, int n, float eps,
 }
 
 void launch_layernorm(void* out, const void* x, const void* w, const void* b,
-                      int n, float eps, hipStream_t stream) {
-  hipLaunchKernelGGL(layernorm_kernel, dim3(1), dim3(256), 0, stream,
-                     (bf16*)out, (const bf16*)x, (const bf16*)w,
-                     (const bf16*)b, n, eps);
+                      int n, float eps, int n_batch, hipStream_t stream) {
+  hipLaunchKernelGGL(layernorm_kernel, dim3(1, n_batch > 0 ? n_batch : 1),
+                     dim3(256), 0, stream, (bf16*)out, (const bf16*)x,
+                     (const bf16*)w, (const bf16*)b, n, eps);
 }
 
 // Turns the runtime (epilogue, norm_kind, rows) of a single GEMV into
@@ -4268,6 +4271,15 @@ int launch_prefill_attn(void* out, const void* qkv, const void* kpool,
   const int n_qtiles = (T + 15) / 16;
   const int blocks = (n_head * n_qtiles + ATTN_WAVES - 1) / ATTN_WAVES;
   const int kv8 = kscale != nullptr;
+  // head size 80 (MHA only) has one kernel of its own in
+  // attn_mha_kernels.hip: no v1 variant, the chunk fixed at 64 keys
+  if (head_size == 80) {
+    if (qpk != 1) return -1;
+    launch_prefill_attn_mha80(out, qkv, kpool, vpool, kscale, vscale, pos0,
+                              slot, layer, n_layers_pool, n_kv_heads, max_seq,
+                              T, scale, stream);
+    return 0;
+  }
   static const bool v1 = [] {
     const char* e = getenv("MDI_PREFILL_V1");
     return e != nullptr && e[0] == '1';

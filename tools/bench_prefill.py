@@ -1,7 +1,16 @@
 #!/usr/bin/env python3
 """A/B: HIP prefill (rope-append + MFMA causal flash attention) vs the
-torch stage prefill (matmul+softmax, S^2 scores) on Llama-3-8B."""
+torch stage prefill (matmul+softmax, S^2 scores), random-init bf16.
 
+  bench_prefill.py [--model NAME] [--lengths 512,2048] [--rounds 2] [--reps 3]
+
+Prompt lengths are clamped to the model's block size.  Every shape is warmed
+up on both paths first; then the two paths alternate, `rounds` times, each
+timing one window of `reps` prefills that ends in a synchronise.  Per length
+it prints every window, and torch/hip of the window means with the spread
+(max - min) / mean of each path's repeats beside it."""
+
+import argparse
 import sys
 import time
 from pathlib import Path
@@ -16,8 +25,15 @@ def main():
     from mdi_llm_amd.models.stages import StarterStage
     from mdi_llm_amd.ops.engine import DecodeEngine
 
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--model", default="Meta-Llama-3-8B-Instruct")
+    ap.add_argument("--lengths", default="512,2048,4096")
+    ap.add_argument("--rounds", type=int, default=2)
+    ap.add_argument("--reps", type=int, default=3)
+    args = ap.parse_args()
+
     dev = torch.device("cuda:0")
-    cfg = ModelConfig.from_name("Meta-Llama-3-8B-Instruct")
+    cfg = ModelConfig.from_name(args.model)
     torch.manual_seed(0)
     torch.set_default_dtype(torch.bfloat16)
     with torch.device(dev):
@@ -26,31 +42,47 @@ def main():
     with torch.no_grad():
         for p in stage.parameters():
             p.normal_(0, 0.02)
-    stage.max_seq_length = 4096
+    stage.max_seq_length = min(4096, cfg.block_size)
     stage.eval()
     stage.set_kv_cache(1)
     eng = DecodeEngine(stage, stage.kv_pool, use_graphs=False)
+    assert eng.supports_hip_prefill, f"{args.model}: no HIP prefill"
 
-    for T in (512, 2048, 4096):
-        toks = torch.randint(0, 128000, (T,), device=dev)
+    lengths = sorted({min(int(t), stage.max_seq_length)
+                      for t in args.lengths.split(",")})
+    prompts = {T: torch.randint(0, cfg.vocab_size, (T,), device=dev)
+               for T in lengths}
 
-        def hip():
-            eng.prefill_prompt(toks, 0, 0)
+    def hip(toks):
+        eng.prefill_prompt(toks, 0, 0)
 
-        def ref():
-            with torch.inference_mode():
-                stage.forward_head(toks.view(1, -1), slot=0, input_pos=0)
+    def ref(toks):
+        with torch.inference_mode():
+            stage.forward_head(toks.view(1, -1), slot=0, input_pos=0)
 
-        for name, fn in (("hip", hip), ("torch", ref)):
-            fn()
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            n = 3
-            for _ in range(n):
-                fn()
-            torch.cuda.synchronize()
-            ms = (time.perf_counter() - t0) / n * 1e3
-            print(f"prefill T={T:5d} {name:>6}: {ms:8.2f} ms", flush=True)
+    paths = (("hip", hip), ("torch", ref))
+    for toks in prompts.values():
+        for _, fn in paths:
+            fn(toks)
+    torch.cuda.synchronize()
+
+    for T, toks in prompts.items():
+        ms = {name: [] for name, _ in paths}
+        for rnd in range(args.rounds):
+            for name, fn in paths:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(args.reps):
+                    fn(toks)
+                torch.cuda.synchronize()
+                ms[name].append((time.perf_counter() - t0) / args.reps * 1e3)
+                print(f"prefill {args.model} T={T:5d} round {rnd} "
+                      f"{name:>6}: {ms[name][-1]:8.2f} ms", flush=True)
+        mean = {k: sum(v) / len(v) for k, v in ms.items()}
+        spread = {k: (max(v) - min(v)) / mean[k] for k, v in ms.items()}
+        print(f"prefill {args.model} T={T:5d} torch/hip "
+              f"{mean['torch'] / mean['hip']:.2f}x  spread hip "
+              f"{spread['hip']:.1%} torch {spread['torch']:.1%}", flush=True)
 
 
 if __name__ == "__main__":

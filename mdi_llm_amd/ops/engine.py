@@ -198,6 +198,99 @@ def dequantize_int4(packed: torch.Tensor, qparams: torch.Tensor,
     return w.view(M, Kp)[:, :K].contiguous()
 
 
+MXFP4_BLOCK = 32
+# e2m1 code (low three bits; bit 3 is the sign) -> magnitude
+_E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+def mxfp4_scale_row_bytes(K: int) -> int:
+    """Bytes of e8m0 scales per row (see quantize_mxfp4)."""
+    nb = -(-K // MXFP4_BLOCK)
+    return ((nb >> 8) * 64 + min(nb & 255, 64)) * 4
+
+
+def _mxfp4_scale_index(K: int, device) -> torch.Tensor:
+    """Byte offset of every block's scale in its row's scale array."""
+    c = torch.arange(-(-K // MXFP4_BLOCK), device=device)
+    return ((c >> 8) * 64 + (c & 63)) * 4 + ((c >> 6) & 3)
+
+
+def _pow2(e: torch.Tensor) -> torch.Tensor:
+    """Exact fp32 2**e for integer e in -126..127, from the bit pattern."""
+    return ((e.to(torch.int32) + 127) << 23).view(torch.float32)
+
+
+def quantize_mxfp4(w: torch.Tensor):
+    """bf16 [M,K] -> (packed uint8 [M,Kp/2], e8m0 scales uint8 [M,SB]).
+
+    OCP MX: blocks of 32 consecutive k share one power-of-two scale 2**e,
+    e = floor(log2(amax)) - 2 clamped to -127..127 (0 for an all-zero
+    block), stored as e + 127; elements are w / 2**e rounded to nearest
+    even onto the signed e2m1 grid {0, .5, 1, 1.5, 2, 3, 4, 6}, saturating
+    at 6.  K is padded to Kp = ceil(K/32)*32 with zero elements, which take
+    no part in a block's amax.
+
+    Layout (what FmtMxfp4 in decode_kernels.hip reads).  Elements: byte j
+    of a block's 16 bytes holds k = 2j in the low nibble and k = 2j+1 in
+    the high nibble.  Scales: not [M, Kp/32] but in the order a wave walks
+    a row: lane l reads blocks l, l+64, l+128, ..., and the four bytes of
+    dword q*64 + l are the scales of blocks q*256 + l + 64*t, t = 0..3, so
+    a lane fetches the scales of four chunks with one load.  A row has
+    SB = mxfp4_scale_row_bytes(K) bytes; bytes no block owns are 127."""
+    assert w.dim() == 2
+    M, K = w.shape
+    nb = -(-K // MXFP4_BLOCK)
+    Kp = nb * MXFP4_BLOCK
+    wf = torch.nn.functional.pad(w.detach().float(), (0, Kp - K))
+    wf = wf.view(M, nb, MXFP4_BLOCK)
+    amax = wf.abs().amax(dim=2)
+    # amax = m * 2**ex with m in [0.5, 1): floor(log2(amax)) = ex - 1
+    e = (torch.frexp(amax)[1] - 3).clamp_(-127, 127)
+    e = torch.where(amax == 0, torch.zeros_like(e), e)
+    # w / 2**e in two exact steps, so 2**-e stays a normal fp32 at e = +-127
+    h = torch.div(e, 2, rounding_mode="floor")
+    a = wf * _pow2(-h)[..., None] * _pow2(h - e)[..., None]
+    neg = a < 0
+    a = a.abs_()
+    # thresholds are the grid's midpoints; a tie goes to the even code
+    code = ((a > 0.25).to(torch.uint8) + (a >= 0.75) + (a > 1.25)
+            + (a >= 1.75) + (a > 2.5) + (a >= 3.5) + (a > 5.0))
+    code = (code | (neg.to(torch.uint8) << 3)).view(M, Kp // 2, 2)
+    packed = code[..., 0] | (code[..., 1] << 4)
+    scales = torch.full((M, mxfp4_scale_row_bytes(K)), 127,
+                        dtype=torch.uint8, device=w.device)
+    scales[:, _mxfp4_scale_index(K, w.device)] = (e + 127).to(torch.uint8)
+    return packed.contiguous(), scales
+
+
+def quantize_mxfp4_slab(slab: torch.Tensor):
+    """Stacked expert slab bf16 [n_e,M,K] -> (packed [n_e,M,Kp/2], scales
+    [n_e,M,SB]); expert e is quantize_mxfp4(slab[e]) bit for bit (one
+    expert at a time: the fp32 temporaries stay one expert large)."""
+    assert slab.dim() == 3
+    n_e, M, K = slab.shape
+    q = torch.empty(n_e, M, -(-K // MXFP4_BLOCK) * 16, dtype=torch.uint8,
+                    device=slab.device)
+    s = torch.empty(n_e, M, mxfp4_scale_row_bytes(K), dtype=torch.uint8,
+                    device=slab.device)
+    for e in range(n_e):
+        q[e], s[e] = quantize_mxfp4(slab[e])
+    return q, s
+
+
+def dequantize_mxfp4(packed: torch.Tensor, scales: torch.Tensor,
+                     K: int) -> torch.Tensor:
+    """Exact inverse mapping of quantize_mxfp4: fp32 [M,K] of e2m1 * 2**e
+    read back from the packed layout (pure torch)."""
+    M = packed.size(0)
+    code = torch.stack([packed & 0xF, packed >> 4], dim=2).long()
+    lut = torch.tensor(_E2M1 + tuple(-v for v in _E2M1),
+                       dtype=torch.float64, device=packed.device)
+    e = scales[:, _mxfp4_scale_index(K, packed.device)].double() - 127.0
+    w = lut[code].view(M, -1, MXFP4_BLOCK) * torch.exp2(e)[..., None]
+    return w.view(M, -1)[:, :K].float().contiguous()
+
+
 class _BlockWeights:
     """Contiguous bf16 views of one block's parameters."""
 
@@ -304,6 +397,32 @@ class _BlockWeights:
             setattr(self, n + "4", packed)
             setattr(self, n[:-2] + "_q", qparams)
 
+    def quantize_mxfp4(self, config) -> None:
+        """Attach packed mxfp4 copies (<name>_wmx) + e8m0 block scales
+        (<name>_smx) for the decode GEMVs.  MoE: the three expert slabs,
+        cached on the mlp module like the fp8 ones (quantize_fp8_experts);
+        the router weight stays bf16."""
+        names = ["attn_w", "proj_w"]
+        if config.mlp_class_name == "LLaMAMoE":
+            mlp, key = self._mlp, self._slab_key
+            cached = getattr(mlp, "_hip_expert_slabs_mxfp4", None)
+            if key is None or cached is None or cached[0] != key:
+                q = tuple(t for w_ in (self.fc1_w, self.fc2_w,
+                                       self.mlp_proj_w)
+                          for t in quantize_mxfp4_slab(w_))
+                cached = (key, q)
+                mlp._hip_expert_slabs_mxfp4 = cached
+            (self.fc1_wmx, self.fc1_smx, self.fc2_wmx, self.fc2_smx,
+             self.mlp_proj_wmx, self.mlp_proj_smx) = cached[1]
+        elif config.mlp_class_name in ("LLaMAMLP", "GemmaMLP"):
+            names += ["mlp_proj_w", "fc1_w", "fc2_w"]
+        else:
+            names += ["mlp_proj_w", "fc_w"]
+        for n in names:
+            packed, scales = quantize_mxfp4(getattr(self, n))
+            setattr(self, n + "mx", packed)
+            setattr(self, n[:-2] + "_smx", scales)
+
 
 class DecodeEngine:
     """Drives the HIP kernels for a stage (Starter or Secondary module)."""
@@ -375,6 +494,14 @@ class DecodeEngine:
         if self.int4:
             for w in self.blocks:
                 w.quantize_int4(cfg)
+        # mxfp4 (OCP e2m1, 32-block e8m0 scales): the 4-bit format gfx950
+        # converts in hardware, and the one that covers MoE expert slabs.
+        # Decode GEMVs only, like fp8 and int4.
+        self.mxfp4 = (self.weight_dtype == "mxfp4"
+                      and self.device.type == "cuda")
+        if self.mxfp4:
+            for w in self.blocks:
+                w.quantize_mxfp4(cfg)
         if self.is_starter:
             self.wte = stage.transformer.wte.weight.detach().contiguous()
             self.lnf_w = stage.transformer.ln_f.weight.detach().contiguous()
@@ -387,6 +514,8 @@ class DecodeEngine:
             if self.int4:
                 self.head_w4, self.head_q = quantize_int4_groupwise(
                     self.head_w)
+            if self.mxfp4:
+                self.head_wmx, self.head_smx = quantize_mxfp4(self.head_w)
             self.head_b = stage.lm_head.bias
             if self.head_b is not None:
                 self.head_b = self.head_b.detach().contiguous()
@@ -474,6 +603,7 @@ class DecodeEngine:
         self._fuse_attn_proj = (
             not self.fp8
             and not self.int4
+            and not self.mxfp4
             and not self.kv8
             and not cfg.parallel_residual
             and cfg.head_size in (64, 128, 256)
@@ -581,9 +711,14 @@ class DecodeEngine:
         """out = epilogue(W @ norm?(x)) for the weight `name` held by `w`
         (a _BlockWeights, or the engine itself for the lm_head), in the
         engine's weight mode: <name>_w bf16, <name>_w8/<name>_s fp8,
-        <name>_w4/<name>_q int4."""
+        <name>_w4/<name>_q int4, <name>_wmx/<name>_smx mxfp4."""
         eps = self.config.norm_eps
-        if self.int4:
+        if self.mxfp4:
+            self.ops.gemv_mxfp4(out, getattr(w, name + "_wmx"),
+                                getattr(w, name + "_smx"), x, bias, res,
+                                epilogue, norm_w, norm_b, norm_kind, eps,
+                                rows)
+        elif self.int4:
             self.ops.gemv_int4(out, getattr(w, name + "_w4"),
                                getattr(w, name + "_q"), x, bias, res,
                                epilogue, norm_w, norm_b, norm_kind, eps,
@@ -683,6 +818,19 @@ class DecodeEngine:
                                  self._r_down, eidx=ej, estride=E * I)
                     res_j = out
                     continue
+                if self.mxfp4:
+                    # estride: bytes of one packed [M, ceil(K/32)*16] slab
+                    ops.gemv_swiglu_mxfp4(
+                        self.act, w.fc1_wmx, w.fc1_smx, w.fc2_wmx,
+                        w.fc2_smx, self.xn, False, None, None, 0, eps,
+                        eidx=ej, estride=I * w.fc1_wmx.size(-1),
+                        escale=self.moe_escale[j:j + 1])
+                    ops.gemv_mxfp4(out, w.mlp_proj_wmx, w.mlp_proj_smx,
+                                   self.act, None, res_j, 1, None, None, 0,
+                                   eps, self._r_down, eidx=ej,
+                                   estride=E * w.mlp_proj_wmx.size(-1))
+                    res_j = out
+                    continue
                 ops.gemv_swiglu(self.act, w.fc1_w, w.fc2_w, self.xn, False,
                                 None, None, 0, eps, eidx=ej,
                                 estride=I * E,
@@ -694,7 +842,12 @@ class DecodeEngine:
             return
         if cfg.mlp_class_name in ("LLaMAMLP", "GemmaMLP"):
             gelu_gate = cfg.mlp_class_name == "GemmaMLP"
-            if self.int4:
+            if self.mxfp4:
+                self.ops.gemv_swiglu_mxfp4(self.act, w.fc1_wmx, w.fc1_smx,
+                                           w.fc2_wmx, w.fc2_smx, inp,
+                                           gelu_gate, norm_w, norm_b, nk,
+                                           eps)
+            elif self.int4:
                 self.ops.gemv_swiglu_int4(self.act, w.fc1_w4, w.fc1_q,
                                           w.fc2_w4, w.fc2_q, inp, gelu_gate,
                                           norm_w, norm_b, nk, eps)

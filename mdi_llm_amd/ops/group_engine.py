@@ -140,6 +140,12 @@ class GroupDecodeEngine:
 
             warnings.warn("grouped decode ignores MDI_WEIGHT_DTYPE=int4 "
                           "(int4 weights serve single-sample decode only)")
+        # and so do mxfp4 weights
+        if os.environ.get("MDI_WEIGHT_DTYPE", "bf16") == "mxfp4":
+            import warnings
+
+            warnings.warn("grouped decode ignores MDI_WEIGHT_DTYPE=mxfp4 "
+                          "(mxfp4 weights serve single-sample decode only)")
         self.fp8 = False
         self.config = cfg
         self.stage = stage

@@ -359,6 +359,97 @@ void gemv_swiglu_int4(torch::Tensor out, torch::Tensor Wg, torch::Tensor gq,
                           (int)norm_kind, cur_stream());
 }
 
+// packed mxfp4 weights [M, ceil(K/32)*16] (uint8) + e8m0 block scales
+// (uint8, mxfp4_scale_row_bytes(K) per row), plain or n stacked expert
+// slabs.  Returns n (0 without eidx).
+inline int64_t check_mxfp4(const c10::optional<torch::Tensor>& eidx,
+                           const torch::Tensor& W, const torch::Tensor& s,
+                           int64_t M, int64_t K, int64_t norm_kind,
+                           int64_t estride, const char* name) {
+  TORCH_CHECK(K % 8 == 0, "K must be a multiple of 8");
+  const int64_t Kp = (K + 31) / 32 * 32;
+  TORCH_CHECK(Kp * 2 <= 64 * 1024, "K too large for the staged mxfp4 GEMV");
+  for (const torch::Tensor* t : {&W, &s})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kUInt8 &&
+                    t->is_contiguous(),
+                name, " and its scales must be contiguous uint8 on GPU");
+  TORCH_CHECK(W.dim() >= 2 && W.size(-1) == Kp / 2, name,
+              ": packed width must be ceil(K/32)*16");
+  const int64_t slab = M * Kp / 2;
+  int64_t n = 0;
+  if (eidx.has_value()) {
+    check_i32(*eidx, "eidx");
+    TORCH_CHECK(eidx->numel() > 0, "eidx is empty");
+    TORCH_CHECK(norm_kind != 2, "expert indirection: no LayerNorm");
+    TORCH_CHECK(W.numel() > 0 && W.numel() % slab == 0, name,
+                ": stacked weight shape");
+    n = W.numel() / slab;
+    TORCH_CHECK(estride == slab, "estride must be M * ceil(K/32)*16");
+  } else {
+    TORCH_CHECK(W.numel() == slab, name, " shape mismatch");
+  }
+  TORCH_CHECK(s.numel() == (n ? n : 1) * M * mxfp4_scale_row_bytes((int)K),
+              name, ": scale array size");
+  return n;
+}
+
+void gemv_mxfp4(torch::Tensor out, torch::Tensor W, torch::Tensor wscale,
+                torch::Tensor x, c10::optional<torch::Tensor> bias,
+                c10::optional<torch::Tensor> res, int64_t epilogue,
+                c10::optional<torch::Tensor> norm_w,
+                c10::optional<torch::Tensor> norm_b, int64_t norm_kind,
+                double eps, int64_t rows, c10::optional<torch::Tensor> eidx,
+                int64_t estride) {
+  check_bf16(out, "out");
+  check_bf16(x, "x");
+  const int K = (int)x.numel();
+  const int M = (int)out.numel();
+  check_gemv_dims(M, K, epilogue, norm_kind);
+  const int64_t n_slab =
+      check_mxfp4(eidx, W, wscale, M, K, norm_kind, estride, "W");
+  const void* bp = opt_bf16_vec(bias, M, "bias");
+  const void* rp = opt_bf16_vec(res, M, "res");
+  const NormPtrs np = check_norm(norm_w, norm_b, norm_kind, K);
+  launch_gemv_mxfp4(out.data_ptr(), W.data_ptr(), wscale.data_ptr(),
+                    x.data_ptr(), bp, rp, np.w, np.b, (float)eps, M, K,
+                    (int)epilogue, (int)norm_kind, (int)rows,
+                    n_slab ? eidx->data_ptr<int>() : nullptr,
+                    (long long)estride, (int)n_slab, cur_stream());
+}
+
+void gemv_swiglu_mxfp4(torch::Tensor out, torch::Tensor Wg,
+                       torch::Tensor gscale, torch::Tensor Wu,
+                       torch::Tensor uscale, torch::Tensor x, bool gelu_gate,
+                       c10::optional<torch::Tensor> norm_w,
+                       c10::optional<torch::Tensor> norm_b, int64_t norm_kind,
+                       double eps, c10::optional<torch::Tensor> eidx,
+                       int64_t estride, c10::optional<torch::Tensor> escale) {
+  check_bf16(out, "out");
+  check_bf16(x, "x");
+  const int K = (int)x.numel();
+  const int M = (int)out.numel();
+  check_gemv_dims(M, K, 0, norm_kind);
+  const int64_t n_slab =
+      check_mxfp4(eidx, Wg, gscale, M, K, norm_kind, estride, "Wg");
+  TORCH_CHECK(check_mxfp4(eidx, Wu, uscale, M, K, norm_kind, estride,
+                          "Wu") == n_slab,
+              "Wu: stacked weight shape");
+  const float* esp = nullptr;
+  if (escale.has_value()) {
+    check_f32(*escale, "escale");
+    TORCH_CHECK(escale->numel() > 0, "escale is empty");
+    esp = escale->data_ptr<float>();
+  }
+  const NormPtrs np = check_norm(norm_w, norm_b, norm_kind, K);
+  launch_gemv_swiglu_mxfp4(out.data_ptr(), Wg.data_ptr(), gscale.data_ptr(),
+                           Wu.data_ptr(), uscale.data_ptr(), x.data_ptr(),
+                           np.w, np.b, (float)eps, M, K, gelu_gate ? 1 : 0,
+                           (int)norm_kind,
+                           n_slab ? eidx->data_ptr<int>() : nullptr,
+                           (long long)estride, (int)n_slab, esp,
+                           cur_stream());
+}
+
 void gemv_swiglu(torch::Tensor out, torch::Tensor Wg, torch::Tensor Wu,
                  torch::Tensor x, bool gelu_gate,
                  c10::optional<torch::Tensor> norm_w,
@@ -1041,6 +1132,25 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("uq"), py::arg("x"), py::arg("gelu_gate"),
         py::arg("norm_w") = c10::nullopt, py::arg("norm_b") = c10::nullopt,
         py::arg("norm_kind") = 0, py::arg("eps") = 1e-5);
+  m.def("gemv_mxfp4", &gemv_mxfp4,
+        "decode GEMV with OCP MXFP4 weights (e2m1, 32-block e8m0 scales)",
+        py::arg("out"), py::arg("W"), py::arg("wscale"), py::arg("x"),
+        py::arg("bias"), py::arg("res"), py::arg("epilogue"),
+        py::arg("norm_w") = c10::nullopt, py::arg("norm_b") = c10::nullopt,
+        py::arg("norm_kind") = 0, py::arg("eps") = 1e-5,
+        py::arg("rows") = 0, py::arg("eidx") = c10::nullopt,
+        py::arg("estride") = 0);
+  m.def("gemv_swiglu_mxfp4", &gemv_swiglu_mxfp4,
+        "fused SwiGLU pair GEMV with OCP MXFP4 weights",
+        py::arg("out"), py::arg("Wg"), py::arg("gscale"), py::arg("Wu"),
+        py::arg("uscale"), py::arg("x"), py::arg("gelu_gate"),
+        py::arg("norm_w") = c10::nullopt, py::arg("norm_b") = c10::nullopt,
+        py::arg("norm_kind") = 0, py::arg("eps") = 1e-5,
+        py::arg("eidx") = c10::nullopt, py::arg("estride") = 0,
+        py::arg("escale") = c10::nullopt);
+  m.def("mxfp4_scale_row_bytes", &mxfp4_scale_row_bytes,
+        "bytes of e8m0 scales per row of an mxfp4 weight with K columns",
+        py::arg("K"));
   m.def("gemv_swiglu", &gemv_swiglu, "fused SwiGLU pair GEMV (+pre-norm)",
         py::arg("out"), py::arg("Wg"), py::arg("Wu"), py::arg("x"),
         py::arg("gelu_gate"), py::arg("norm_w") = c10::nullopt,

@@ -57,6 +57,29 @@ void launch_gemv_swiglu_int4(void* out, const void* Wg, const void* gq,
                              float eps, int M, int K, int gelu_gate,
                              int norm_kind, hipStream_t stream);
 
+// OCP MXFP4 variants: W is [M, Kp/2] packed e2m1 pairs with
+// Kp = ceil(K/32)*32 (byte j of a 16 B block: k = 2j low nibble, 2j+1 high),
+// wscale the e8m0 block scales, mxfp4_scale_row_bytes(K) per row in the
+// lane-major order FmtMxfp4 documents; K is the unpadded length of x.
+// With eidx, W and wscale hold n_slab stacked copies and estride is the
+// byte size of one packed slab.
+int mxfp4_scale_row_bytes(int K);
+
+void launch_gemv_mxfp4(void* out, const void* W, const void* wscale,
+                       const void* x, const void* bias, const void* res,
+                       const void* norm_w, const void* norm_b, float eps,
+                       int M, int K, int epilogue, int norm_kind, int rows,
+                       const int* eidx, long long estride, int n_slab,
+                       hipStream_t stream);
+
+void launch_gemv_swiglu_mxfp4(void* out, const void* Wg, const void* gscale,
+                              const void* Wu, const void* uscale,
+                              const void* x, const void* norm_w,
+                              const void* norm_b, float eps, int M, int K,
+                              int gelu_gate, int norm_kind, const int* eidx,
+                              long long estride, int n_slab,
+                              const float* escale, hipStream_t stream);
+
 void launch_gemv_swiglu(void* out, const void* Wg, const void* Wu,
                         const void* x, const void* norm_w, const void* norm_b,
                         float eps, int M, int K, int gelu_gate, int norm_kind,

@@ -1308,6 +1308,54 @@ DEVINL float dot32_int4(const i32x4_t wq, const x32w& x, unsigned qp,
 }
 
 // ---------------------------------------------------------------------------
+// OCP MXFP4 weights: e2m1 elements in blocks of 32 consecutive k that share
+// one e8m0 (power-of-two) scale.  Rows are zero-padded to Kp = ceil(K/32)*32,
+// Kp/2 bytes: one lane's 16 B load is exactly ONE block, byte j of it holds
+// k = 2j in the low nibble and k = 2j+1 in the high one.  That is the order
+// v_cvt_scalef32_pk_bf16_fp4 unpacks for free: with byte_sel = j it turns
+// byte j of a word into the bf16 pair (w[2j], w[2j+1]) * scale, lined up
+// with the LDS word (x[2j], x[2j+1]) for v_dot2c_f32_bf16 — one convert and
+// one dot product per TWO weights, no zero-point, no group sums.  The
+// products e2m1 * 2^e are exact in bf16, so the kernel adds no weight error.
+//
+// Scales are laid out for the wave's access pattern, not [M][Kp/32]: lane l
+// visits blocks l, l+64, l+128, ... of a row, and dword (q*64 + l) of the
+// row's scale array holds the e8m0 bytes of blocks q*256 + l + 64*{0,1,2,3}
+// (byte t = block + 64t).  A lane loads that dword once per four chunks,
+// and a wave's 64 dwords are one contiguous 256 B read.  A row has
+// mxfp4_scale_dwords(K) dwords; unused bytes are 127 (2^0).
+// ---------------------------------------------------------------------------
+__host__ __device__ inline int mxfp4_scale_dwords(int K) {
+  const int nb = (K + 31) >> 5;  // blocks per row
+  const int tail = nb & 255;
+  return (nb >> 8) * 64 + (tail < 64 ? tail : 64);
+}
+
+// one 16 B load (one block) against the lane's x; scale is the block's 2^e
+DEVINL float dot32_mxfp4(const i32x4_t wq, const x32w& x, float scale) {
+  float d0 = 0.f, d1 = 0.f;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const unsigned w = (unsigned)wq[q];
+    const i32x4_t xq = x.v[q];
+    // byte_sel is an immediate of the instruction: written out, not looped
+    d0 = __builtin_amdgcn_fdot2_f32_bf16(
+        __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 0),
+        __builtin_bit_cast(bf16x2_t, (unsigned)xq[0]), d0, false);
+    d1 = __builtin_amdgcn_fdot2_f32_bf16(
+        __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 1),
+        __builtin_bit_cast(bf16x2_t, (unsigned)xq[1]), d1, false);
+    d0 = __builtin_amdgcn_fdot2_f32_bf16(
+        __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 2),
+        __builtin_bit_cast(bf16x2_t, (unsigned)xq[2]), d0, false);
+    d1 = __builtin_amdgcn_fdot2_f32_bf16(
+        __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 3),
+        __builtin_bit_cast(bf16x2_t, (unsigned)xq[3]), d1, false);
+  }
+  return d0 + d1;
+}
+
+// ---------------------------------------------------------------------------
 // Weight formats of the staged GEMVs.  The two skeletons below are written
 // once; a format struct carries exactly what differs between bf16, fp8 and
 // int4 weights.  Offsets and strides are in the format's own units (elem_t):
@@ -1318,6 +1366,8 @@ DEVINL float dot32_int4(const i32x4_t wq, const x32w& x, unsigned qp,
 //   load / load_x    non-temporal weight chunk / its staged x
 //   aux_row          the row's side data as accum wants it
 //   accum            acc += chunk . x, in the format's fixed operation order
+//   carry_t          per-row state accum keeps from one chunk to the next
+//                    (empty unless the format reuses side data across chunks)
 //   row_scale        per-row factor applied after the norm post-scale
 //   slab / slab_aux  expert-slab index read from eidx, and the side data's
 //                    offset for it (formats with SLABS only)
@@ -1327,6 +1377,7 @@ struct FmtBf16 {
   using aux_t = void;  // no side data
   using chunk_t = bf16x8;
   using xchunk_t = bf16x8;
+  struct carry_t {};
   static constexpr int STEP = 8;  // 8 k per chunk
   static constexpr bool SLABS = true;
   static constexpr bool SWIGLU_PREFETCH = true;
@@ -1341,14 +1392,14 @@ struct FmtBf16 {
     return nullptr;
   }
   static DEVINL void accum(float& acc, const chunk_t& w, const xchunk_t& x,
-                           const void*) {
+                           const void*, carry_t&) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc += b2f(w.v[j]) * b2f(x.v[j]);
   }
   static DEVINL float row_scale(float a, const void*, int) { return a; }
   // the index is used as it comes, as in gemv_direct_kernel
   static DEVINL int slab(const int* eidx, int) { return eidx[0]; }
-  static DEVINL const void* slab_aux(const void* aux, int, int) {
+  static DEVINL const void* slab_aux(const void* aux, int, int, int) {
     return aux;
   }
 };
@@ -1359,6 +1410,7 @@ struct FmtFp8 {
   using aux_t = float;
   using chunk_t = i32x4_t;
   using xchunk_t = const bf16*;  // dot16_fp8 reads LDS itself
+  struct carry_t {};
   static constexpr int STEP = 16;  // 16 k per chunk
   static constexpr bool SLABS = true;
   // with the prefetched pair the fp8 SwiGLU compiles to 114 VGPRs instead
@@ -1377,7 +1429,7 @@ struct FmtFp8 {
     return aux;
   }
   static DEVINL void accum(float& acc, const chunk_t& w, xchunk_t x,
-                           const float*) {
+                           const float*, carry_t&) {
     acc += dot16_fp8(reinterpret_cast<const unsigned*>(&w), x);
   }
   static DEVINL float row_scale(float a, const float* wscale, int rw) {
@@ -1388,7 +1440,7 @@ struct FmtFp8 {
   static DEVINL int slab(const int* eidx, int n_slab) {
     return min(max(eidx[0], 0), n_slab - 1);
   }
-  static DEVINL const float* slab_aux(const float* aux, int e, int M) {
+  static DEVINL const float* slab_aux(const float* aux, int e, int M, int) {
     return aux + (size_t)e * M;
   }
 };
@@ -1410,6 +1462,7 @@ struct FmtInt4 {
     int g;       // the chunk's group
     float gsum;  // and that group's sum of x
   };
+  struct carry_t {};
   static constexpr int STEP = 16;  // 32 k per chunk
   static constexpr bool SLABS = false;
   static constexpr bool SWIGLU_PREFETCH = true;
@@ -1434,10 +1487,72 @@ struct FmtInt4 {
     return qparams + rw * (padded(K) >> 7);
   }
   static DEVINL void accum(float& acc, const chunk_t& w, const xchunk_t& x,
-                           const unsigned* qrow) {
+                           const unsigned* qrow, carry_t&) {
     acc += dot32_int4(w, x.xv, qrow[x.g], x.gsum);
   }
   static DEVINL float row_scale(float a, const unsigned*, int) { return a; }
+};
+
+// aux = the rows' scale dwords [M][mxfp4_scale_dwords(K)] (see above);
+// offsets and strides are packed bytes (two k each)
+struct FmtMxfp4 {
+  using elem_t = unsigned char;
+  using aux_t = unsigned;
+  using chunk_t = i32x4_t;
+  struct xchunk_t {
+    x32w xv;
+    int d;   // the chunk's scale dword in its row
+    int sh;  // and the bit offset of its byte there (wave-uniform)
+  };
+  struct carry_t {
+    unsigned s;  // the scale dword of the current four chunks
+  };
+  static constexpr int STEP = 16;  // 32 k per chunk
+  static constexpr bool SLABS = true;
+  // the prefetched pair compiles to 68-70 VGPRs instead of 60-62,
+  // occupancy 7 instead of 8 (profiles/mxfp4_weights.md): one wave, not the
+  // three fp8 would lose, so the early loads stay
+  static constexpr bool SWIGLU_PREFETCH = true;
+  static DEVINL int padded(int K) { return (K + 31) & ~31; }
+  static int smem_bytes(int K) {
+    return ((K + 31) & ~31) * (int)sizeof(bf16);
+  }
+  static DEVINL int stride(int K) { return padded(K) >> 1; }
+  // zero-fill the staged x up to the padded K (K is a multiple of 8)
+  static DEVINL void stage_extra(bf16* xs, int K) {
+    const int Kp = padded(K);
+    if (Kp == K) return;  // uniform: no barrier needed
+    for (int i = K + threadIdx.x * 8; i < Kp; i += blockDim.x * 8)
+      *reinterpret_cast<int4*>(xs + i) = make_int4(0, 0, 0, 0);
+    __syncthreads();
+  }
+  static DEVINL chunk_t load(const unsigned char* p) {
+    return load16_nt_u8(p);
+  }
+  // i = 16 * (lane + 64 t): dword (t/4)*64 + lane, byte t%4
+  static DEVINL xchunk_t load_x(const bf16* xs, int, int i) {
+    const int sh = __builtin_amdgcn_readfirstlane((i >> 7) & 24);
+    return {load_x32(xs + i * 2), ((i >> 12) << 6) | ((i >> 4) & 63), sh};
+  }
+  static DEVINL const unsigned* aux_row(const unsigned* aux, size_t rw,
+                                        int K) {
+    return aux + rw * mxfp4_scale_dwords(K);
+  }
+  static DEVINL void accum(float& acc, const chunk_t& w, const xchunk_t& x,
+                           const unsigned* srow, carry_t& c) {
+    if (x.sh == 0) c.s = srow[x.d];  // first of four chunks: fetch
+    const float scale = __uint_as_float(((c.s >> x.sh) & 0xFFu) << 23);
+    acc += dot32_mxfp4(w, x.xv, scale);
+  }
+  static DEVINL float row_scale(float a, const unsigned*, int) { return a; }
+  // clamped like FmtFp8::slab; the scale rows are stacked [n_slab, M]
+  static DEVINL int slab(const int* eidx, int n_slab) {
+    return min(max(eidx[0], 0), n_slab - 1);
+  }
+  static DEVINL const unsigned* slab_aux(const unsigned* aux, int e, int M,
+                                         int K) {
+    return aux + (size_t)e * M * mxfp4_scale_dwords(K);
+  }
 };
 
 // Staged single GEMV.  eidx/estride select an expert slab from stacked
@@ -1458,7 +1573,7 @@ __global__ void gemv_staged_kernel(
     if (eidx != nullptr) {
       const int e = Fmt::slab(eidx, n_slab);
       W += (size_t)e * (size_t)estride;
-      aux = Fmt::slab_aux(aux, e, M);
+      aux = Fmt::slab_aux(aux, e, M, K);
     }
   }
   const int stride = Fmt::stride(K);
@@ -1487,6 +1602,7 @@ __global__ void gemv_staged_kernel(
     const typename Fmt::elem_t* wrow[ROWS];
     const typename Fmt::aux_t* arow[ROWS];
     float acc[ROWS];
+    typename Fmt::carry_t car[ROWS];
 #pragma unroll
     for (int r = 0; r < ROWS; ++r) {
       const size_t rw = (size_t)min(row + r, M - 1);
@@ -1499,14 +1615,15 @@ __global__ void gemv_staged_kernel(
       // peeled first chunk: consume the pre-barrier prefetch
       const typename Fmt::xchunk_t xv = Fmt::load_x(xs, K, istart);
 #pragma unroll
-      for (int r = 0; r < ROWS; ++r) Fmt::accum(acc[r], wpre[r], xv, arow[r]);
+      for (int r = 0; r < ROWS; ++r)
+        Fmt::accum(acc[r], wpre[r], xv, arow[r], car[r]);
       istart += 64 * Fmt::STEP;
     }
     for (int i = istart; i < stride; i += 64 * Fmt::STEP) {
       const typename Fmt::xchunk_t xv = Fmt::load_x(xs, K, i);
 #pragma unroll
       for (int r = 0; r < ROWS; ++r)
-        Fmt::accum(acc[r], Fmt::load(wrow[r] + i), xv, arow[r]);
+        Fmt::accum(acc[r], Fmt::load(wrow[r] + i), xv, arow[r], car[r]);
     }
 #pragma unroll
     for (int r = 0; r < ROWS; ++r) acc[r] = wave_reduce_sum(acc[r]);
@@ -1544,8 +1661,8 @@ __global__ void gemv_swiglu_kernel(
       const size_t off = (size_t)e * (size_t)estride;
       Wg += off;
       Wu += off;
-      gaux = Fmt::slab_aux(gaux, e, M);
-      uaux = Fmt::slab_aux(uaux, e, M);
+      gaux = Fmt::slab_aux(gaux, e, M, K);
+      uaux = Fmt::slab_aux(uaux, e, M, K);
     }
   }
   const float oscale = (escale != nullptr) ? escale[0] : 1.f;
@@ -1575,19 +1692,20 @@ __global__ void gemv_swiglu_kernel(
     const typename Fmt::aux_t* gq = Fmt::aux_row(gaux, (size_t)row, K);
     const typename Fmt::aux_t* uq = Fmt::aux_row(uaux, (size_t)row, K);
     float ga = 0.f, ua = 0.f;
+    typename Fmt::carry_t gc, uc;
     int istart = lane * Fmt::STEP;
     if (row == row0 && pre_ok) {
       const typename Fmt::xchunk_t xv = Fmt::load_x(xs, K, istart);
-      Fmt::accum(ga, gpre, xv, gq);
-      Fmt::accum(ua, upre, xv, uq);
+      Fmt::accum(ga, gpre, xv, gq, gc);
+      Fmt::accum(ua, upre, xv, uq, uc);
       istart += 64 * Fmt::STEP;
     }
     for (int i = istart; i < stride; i += 64 * Fmt::STEP) {
       const typename Fmt::chunk_t gw = Fmt::load(grow + i);
       const typename Fmt::chunk_t uw = Fmt::load(urow + i);
       const typename Fmt::xchunk_t xv = Fmt::load_x(xs, K, i);
-      Fmt::accum(ga, gw, xv, gq);
-      Fmt::accum(ua, uw, xv, uq);
+      Fmt::accum(ga, gw, xv, gq, gc);
+      Fmt::accum(ua, uw, xv, uq, uc);
     }
     ga = wave_reduce_sum(ga) * nscale;
     ua = wave_reduce_sum(ua) * nscale;
@@ -3781,7 +3899,7 @@ void launch_gemv(void* out, const void* W, const void* x, const void* bias,
   });
 }
 
-// fp8 and int4 single GEMVs: always the staged form
+// fp8, int4 and mxfp4 single GEMVs: always the staged form
 template <class Fmt>
 static void launch_gemv_staged(const GemvArgs& a, int epilogue, int norm_kind,
                                int rows, hipStream_t stream) {
@@ -3813,6 +3931,19 @@ void launch_gemv_int4(void* out, const void* W, const void* qparams,
                                eps, M, K, nullptr, 0, 0},
                               epilogue, norm_kind, rows, stream);
 }
+
+void launch_gemv_mxfp4(void* out, const void* W, const void* wscale,
+                       const void* x, const void* bias, const void* res,
+                       const void* norm_w, const void* norm_b, float eps,
+                       int M, int K, int epilogue, int norm_kind, int rows,
+                       const int* eidx, long long estride, int n_slab,
+                       hipStream_t stream) {
+  launch_gemv_staged<FmtMxfp4>({out, W, wscale, x, bias, res, norm_w, norm_b,
+                                eps, M, K, eidx, estride, n_slab},
+                               epilogue, norm_kind, rows, stream);
+}
+
+int mxfp4_scale_row_bytes(int K) { return mxfp4_scale_dwords(K) * 4; }
 
 // the SwiGLU pair of any format; an out-of-range norm_kind runs as 0
 template <class Fmt>
@@ -3860,6 +3991,18 @@ void launch_gemv_swiglu_int4(void* out, const void* Wg, const void* gq,
   launch_swiglu<FmtInt4>(out, Wg, gq, Wu, uq, x, norm_w, norm_b, eps, M, K,
                          gelu_gate, norm_kind, nullptr, 0, 0, nullptr,
                          stream);
+}
+
+void launch_gemv_swiglu_mxfp4(void* out, const void* Wg, const void* gscale,
+                              const void* Wu, const void* uscale,
+                              const void* x, const void* norm_w,
+                              const void* norm_b, float eps, int M, int K,
+                              int gelu_gate, int norm_kind, const int* eidx,
+                              long long estride, int n_slab,
+                              const float* escale, hipStream_t stream) {
+  launch_swiglu<FmtMxfp4>(out, Wg, gscale, Wu, uscale, x, norm_w, norm_b,
+                          eps, M, K, gelu_gate, norm_kind, eidx, estride,
+                          n_slab, escale, stream);
 }
 
 void launch_gemv_swiglu(void* out, const void* Wg, const void* Wu,

@@ -22,6 +22,20 @@ once per step however many tokens chose it) and ``moe_group_combine``.
 With MDI_WEIGHT_DTYPE=fp8 the expert GEMMs read fp8 slabs
 (``moe_group_swiglu_fp8`` / ``moe_group_down_fp8``, ``moe_fp8``); the dense
 GEMMs stay bf16.
+
+With MDI_WEIGHT_DTYPE=mxfp4 a dense stage (LLaMAMLP / GemmaMLP) on the GPU
+with 16 <= B <= 128 reads every dense weight as packed MXFP4 (4.25 bits per
+weight, the tensors of ``quantize_mxfp4``) through the hand-written fp4-fed
+M-tile MFMA GEMMs: ``mtile_gemm_mxfp4`` for qkv, proj (+residual), down
+(+residual) and the lm_head, ``mtile_swiglu_mxfp4`` for gate and up in one
+launch (``_run_blocks_mxfp4``, ``self.mxfp4``).  Smaller groups, MoE stages,
+the CPU and shapes the kernels refuse keep the bf16 path and warn.
+Measured on Llama-3-8B (``profiles/group_mxfp4.md``): per shape the ops beat
+the bf16 library GEMMs at B=16 (all but down, 0.80x) and proj at B=32, and
+are SLOWER on every shape at B=64 and B=128; end to end the path is slower than
+bf16 at group size 32 (0.92x), 64 (0.62x) and 128 (0.53x); B=16 end to end
+was not measured.  The kernel is bound by its convert / LDS / MFMA issue,
+not by the weight stream.  It is opt-in and off by default.
 """
 
 from __future__ import annotations
@@ -85,6 +99,28 @@ def _moe_group_supported(config: ModelConfig) -> bool:
     )
 
 
+# group sizes served by mtile_gemm_mxfp4 in the engine: the kernel takes
+# B >= 1, but below one 16-wide MFMA column tile the library GEMM on bf16
+# weights is kept (no measurement there)
+MXFP4_MIN_GROUP = 16
+MXFP4_MAX_GROUP = 128
+
+
+def _mxfp4_group_supported(config: ModelConfig, starter: bool,
+                           max_k: int) -> bool:
+    """The shape rule of mtile_gemm_mxfp4 / mtile_swiglu_mxfp4 (K % 8 == 0,
+    32 <= K <= max_k = ops.MTILE_MXFP4_MAX_K, M % 16 == 0) on every dense
+    GEMM of a stage: exactly what the ops accept at every 1 <= B <= 128."""
+    if config.mlp_class_name not in ("LLaMAMLP", "GemmaMLP"):
+        return False
+    E, I = config.n_embd, config.intermediate_size or 0
+    ks = (E, config.n_head * config.head_size, I)
+    ms = (config.qkv_dim, E, I) + (
+        (config.padded_vocab_size,) if starter else ())
+    return (all(k % 8 == 0 and 32 <= k <= max_k for k in ks)
+            and all(m % 16 == 0 and m >= 16 for m in ms))
+
+
 def group_engine_supported(config: ModelConfig) -> bool:
     if not (engine_supported(config)
             and config.norm_class_name == "RMSNorm"):
@@ -140,12 +176,27 @@ class GroupDecodeEngine:
 
             warnings.warn("grouped decode ignores MDI_WEIGHT_DTYPE=int4 "
                           "(int4 weights serve single-sample decode only)")
-        # and so do mxfp4 weights
+        # mxfp4 weights: the dense GEMMs of a group of 16..128 run on the
+        # hand-written fp4-fed M-tile kernels (_run_blocks_mxfp4); smaller
+        # groups, MoE stages, the CPU and refused shapes keep bf16
+        self.mxfp4 = (
+            os.environ.get("MDI_WEIGHT_DTYPE", "bf16") == "mxfp4"
+            and not self.moe
+            and next(stage.parameters()).device.type == "cuda"
+            and MXFP4_MIN_GROUP <= group_size <= MXFP4_MAX_GROUP
+            and _mxfp4_group_supported(cfg, hasattr(stage, "lm_head"),
+                                       self.ops.MTILE_MXFP4_MAX_K))
         if os.environ.get("MDI_WEIGHT_DTYPE", "bf16") == "mxfp4":
             import warnings
 
-            warnings.warn("grouped decode ignores MDI_WEIGHT_DTYPE=mxfp4 "
-                          "(mxfp4 weights serve single-sample decode only)")
+            if self.mxfp4:
+                warnings.warn("grouped decode: MDI_WEIGHT_DTYPE=mxfp4 applies "
+                              "to qkv, proj, the MLP and the lm_head "
+                              "(mtile_gemm_mxfp4 / mtile_swiglu_mxfp4)")
+            else:
+                warnings.warn("grouped decode ignores MDI_WEIGHT_DTYPE=mxfp4 "
+                              "(mxfp4 weights serve single-sample decode "
+                              "only)")
         self.fp8 = False
         self.config = cfg
         self.stage = stage
@@ -168,10 +219,17 @@ class GroupDecodeEngine:
         if self.moe_fp8:
             for w in self.blocks:
                 w.quantize_fp8_experts()
+        if self.mxfp4:
+            for w in self.blocks:
+                w.quantize_mxfp4(cfg)
         if self.is_starter:
             self.wte = stage.transformer.wte.weight.detach().contiguous()
             self.lnf_w = stage.transformer.ln_f.weight.detach().contiguous()
             self.head_w = stage.lm_head.weight.detach().contiguous()
+            if self.mxfp4:
+                from .engine import quantize_mxfp4
+
+                self.head_wmx, self.head_smx = quantize_mxfp4(self.head_w)
             if self.fp8:
                 from .engine import quantize_fp8_rowwise
 
@@ -196,8 +254,8 @@ class GroupDecodeEngine:
         # B=32 +0.2% noise, B=64 -2%).  Default OFF — a documented
         # measured refutation; MDI_MTILE=proj|all opts in.
         mt_env = os.environ.get("MDI_MTILE", "0")
-        if self.moe:
-            mt_env = "0"  # the expert GEMMs are their own kernels
+        if self.moe or self.mxfp4:
+            mt_env = "0"  # the expert / mxfp4 GEMMs are their own kernels
         shapes_ok = (B in (16, 32, 64, 128)
                      and all(self._mtile_k_ok(B, k)
                              for k in (E, n_head * hs, I)))
@@ -212,6 +270,9 @@ class GroupDecodeEngine:
             self.A2 = torch.zeros(B, E, **bf)
         if self.use_mtile:
             self.G = torch.zeros(B, I, **bf)
+            self.U2 = torch.zeros(B, I, **bf)
+        if self.mxfp4:
+            self.A2 = torch.zeros(B, E, **bf)
             self.U2 = torch.zeros(B, I, **bf)
         if self.moe:
             # routing + expert-major workspaces: static sizes (B*k rows),
@@ -308,7 +369,37 @@ class GroupDecodeEngine:
             ops.mtile_gemm(self.X, w.mlp_proj_w, self.U2, w.mlp_proj_b,
                            self.A2)
 
+    def _run_blocks_mxfp4(self) -> None:
+        """Block stack on the fp4-fed M-tile MFMA GEMMs: every dense weight
+        is read as packed mxfp4, gate and up share one launch and one
+        staged X, bias and residual adds sit in the GEMM epilogues.  All
+        outputs are preallocated, so the step captures as one hipGraph."""
+        cfg = self.config
+        scale = 1.0 / (cfg.head_size ** 0.5)
+        gelu_gate = cfg.mlp_class_name == "GemmaMLP"
+        ops = self.ops
+        for li, w in enumerate(self.blocks):
+            xn = self._rms(self.X, w.norm1_w, self.XN)
+            ops.mtile_gemm_mxfp4(self.QKV, w.attn_wmx, w.attn_smx, xn,
+                                 w.attn_b, None)
+            ops.attn_decode(
+                self.Y, self.part_o, self.part_ml, self.QKV, self.kv_pool.k,
+                self.kv_pool.v, self.cos, self.sin, self.pos, self.slots,
+                li, self.n_chunks, scale, self.B,
+                kscale=self.kv_pool.kscale, vscale=self.kv_pool.vscale,
+            )
+            ops.mtile_gemm_mxfp4(self.A2, w.proj_wmx, w.proj_smx, self.Y,
+                                 w.proj_b, self.X)
+            hn = self._rms(self.A2, w.norm2_w, self.HN)
+            ops.mtile_swiglu_mxfp4(self.U2, w.fc1_wmx, w.fc1_smx, w.fc2_wmx,
+                                   w.fc2_smx, hn, gelu_gate)
+            ops.mtile_gemm_mxfp4(self.X, w.mlp_proj_wmx, w.mlp_proj_smx,
+                                 self.U2, w.mlp_proj_b, self.A2)
+
     def _run_blocks(self) -> None:
+        if self.mxfp4:
+            self._run_blocks_mxfp4()
+            return
         if self.use_mtile:
             self._run_blocks_mtile()
             return
@@ -402,7 +493,10 @@ class GroupDecodeEngine:
 
     def _tail_seq(self) -> None:
         xn = self._rms(self.X, self.lnf_w, self.XN)
-        if self.use_mtile and self.head_w.size(0) % 16 == 0:
+        if self.mxfp4:
+            self.ops.mtile_gemm_mxfp4(self.LOGITS, self.head_wmx,
+                                      self.head_smx, xn, None, None)
+        elif self.use_mtile and self.head_w.size(0) % 16 == 0:
             self.ops.mtile_gemm(self.LOGITS, self.head_w, xn, None, None)
         elif self.fp8:
             self.LOGITS.copy_(
@@ -438,6 +532,8 @@ class GroupDecodeEngine:
     _LANE_ATTRS = ("X", "XN", "HN", "QKV", "Y", "part_o", "part_ml",
                    "LOGITS", "sample_scratch", "tokens", "slots",
                    "slots_long", "pos",
+                   # outputs of the mxfp4 GEMMs (a lane needs its own)
+                   "A2", "U2",
                    # grouped MoE routing + expert-major workspaces
                    "moe_eidx", "moe_escale", "moe_count", "moe_offset",
                    "moe_perm", "moe_inv", "ACT", "D")

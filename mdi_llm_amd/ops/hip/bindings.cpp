@@ -1000,6 +1000,89 @@ void mtile_gemm(torch::Tensor Y, torch::Tensor W, torch::Tensor X,
               " M=", M);
 }
 
+// shared argument checks of the two mxfp4 M-tile ops; returns (B, M, K)
+struct MtileMxDims {
+  int B, M, K;
+};
+
+inline MtileMxDims check_mtile_mxfp4(const torch::Tensor& Y,
+                                     const torch::Tensor& Wq,
+                                     const torch::Tensor& X,
+                                     const char* op) {
+  check_bf16(Y, "Y");
+  check_bf16(X, "X");
+  TORCH_CHECK(X.dim() == 2 && Wq.dim() == 2, op,
+              ": packed weights and X must be 2-D");
+  const int64_t B = X.size(0), K = X.size(1), M = Wq.size(0);
+  TORCH_CHECK(B >= 1 && B <= 128, op, ": 1 <= B <= 128, got ", B);
+  TORCH_CHECK(K % 8 == 0 && K >= 32 && K <= MTILE_MXFP4_MAX_K, op,
+              ": K % 8 == 0 and 32 <= K <= ", MTILE_MXFP4_MAX_K,
+              " (the scale rows of a block's rows stay in LDS), got ", K);
+  TORCH_CHECK(M >= 16 && M % 16 == 0, op, ": M % 16 == 0, got ", M);
+  TORCH_CHECK(Y.numel() == B * M, op, ": Y must hold B * M elements");
+  TORCH_CHECK(X.device() == Y.device() && Wq.device() == Y.device(), op,
+              ": all tensors must be on one device");
+  TORCH_CHECK((uintptr_t)X.data_ptr() % 16 == 0, op,
+              ": X must be 16-byte aligned");
+  return {(int)B, (int)M, (int)K};
+}
+
+// one packed mxfp4 matrix [M, ceil(K/32)*16] (uint8) and its scale rows
+// [M, mxfp4_scale_row_bytes(K)] (uint8) for the M-tile ops
+inline void check_mtile_mx_weight(const char* op, const char* name,
+                                  const torch::Tensor& W,
+                                  const torch::Tensor& s, int M, int K,
+                                  const torch::Device& dev) {
+  for (const torch::Tensor* t : {&W, &s})
+    TORCH_CHECK(t->is_cuda() && t->device() == dev &&
+                    t->scalar_type() == torch::kUInt8 && t->is_contiguous(),
+                op, ": ", name,
+                " and its scales must be contiguous uint8 on Y's device");
+  const int64_t wb = (int64_t)(K + 31) / 32 * 16;
+  TORCH_CHECK(W.dim() == 2 && W.size(0) == M && W.size(1) == wb, op, ": ",
+              name, " must be [M, ceil(K/32)*16] = [", M, ", ", wb, "]");
+  TORCH_CHECK(s.numel() == (int64_t)M * mxfp4_scale_row_bytes(K), op, ": ",
+              name, " needs M * mxfp4_scale_row_bytes(K) scale bytes");
+  // 16 B weight loads and dword scale loads
+  TORCH_CHECK((uintptr_t)W.data_ptr() % 16 == 0 &&
+                  (uintptr_t)s.data_ptr() % 4 == 0,
+              op, ": ", name, " must be 16-byte, its scales dword aligned");
+}
+
+void mtile_gemm_mxfp4(torch::Tensor Y, torch::Tensor Wq, torch::Tensor Ws,
+                      torch::Tensor X, c10::optional<torch::Tensor> bias,
+                      c10::optional<torch::Tensor> res) {
+  const char* op = "mtile_gemm_mxfp4";
+  const MtileMxDims d = check_mtile_mxfp4(Y, Wq, X, op);
+  check_mtile_mx_weight(op, "Wq", Wq, Ws, d.M, d.K, Y.device());
+  const void* bp = opt_bf16_vec(bias, d.M, "bias");
+  const void* rp = opt_bf16_vec(res, (int64_t)d.B * d.M, "res");
+  TORCH_CHECK((!bias.has_value() || bias->device() == Y.device()) &&
+                  (!res.has_value() || res->device() == Y.device()),
+              op, ": all tensors must be on one device");
+  const int rc = launch_mtile_mxfp4(Y.data_ptr(), Wq.data_ptr(),
+                                    Ws.data_ptr(), nullptr, nullptr,
+                                    X.data_ptr(), bp, rp, d.B, d.M, d.K, 0,
+                                    cur_stream());
+  TORCH_CHECK(rc == 0, op, ": unsupported shape B=", d.B, " K=", d.K,
+              " M=", d.M);
+}
+
+void mtile_swiglu_mxfp4(torch::Tensor ACT, torch::Tensor Wgq,
+                        torch::Tensor Wgs, torch::Tensor Wuq,
+                        torch::Tensor Wus, torch::Tensor X, bool gelu) {
+  const char* op = "mtile_swiglu_mxfp4";
+  const MtileMxDims d = check_mtile_mxfp4(ACT, Wgq, X, op);
+  check_mtile_mx_weight(op, "Wgq", Wgq, Wgs, d.M, d.K, ACT.device());
+  check_mtile_mx_weight(op, "Wuq", Wuq, Wus, d.M, d.K, ACT.device());
+  const int rc = launch_mtile_mxfp4(
+      ACT.data_ptr(), Wgq.data_ptr(), Wgs.data_ptr(), Wuq.data_ptr(),
+      Wus.data_ptr(), X.data_ptr(), nullptr, nullptr, d.B, d.M, d.K,
+      gelu ? 1 : 0, cur_stream());
+  TORCH_CHECK(rc == 0, op, ": unsupported shape B=", d.B, " K=", d.K,
+              " M=", d.M);
+}
+
 void route_env(torch::Tensor hdr, torch::Tensor slot_out,
                torch::Tensor pos_table, int64_t dummy_slot) {
   check_i32(hdr, "hdr");
@@ -1254,6 +1337,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "grouped-decode M-tile MFMA GEMM (bulk LDS-staged X, nt W stream)",
         py::arg("Y"), py::arg("W"), py::arg("X"), py::arg("bias"),
         py::arg("res"));
+  m.attr("MTILE_MXFP4_MAX_K") = (int64_t)MTILE_MXFP4_MAX_K;
+  m.def("mtile_gemm_mxfp4", &mtile_gemm_mxfp4,
+        "grouped-decode M-tile MFMA GEMM on mxfp4 weights: Y[B,M] = X[B,K] @ "
+        "dequant(Wq)^T (+bias[M]) (+res[B,M]); Wq/Ws as quantize_mxfp4 "
+        "returns them, 1 <= B <= 128, K % 8 == 0, 32 <= K <= "
+        "MTILE_MXFP4_MAX_K (32768), M % 16 == 0",
+        py::arg("Y"), py::arg("Wq"), py::arg("Ws"), py::arg("X"),
+        py::arg("bias"), py::arg("res"));
+  m.def("mtile_swiglu_mxfp4", &mtile_swiglu_mxfp4,
+        "fused gate/up of the grouped MLP on mxfp4 weights: ACT[B,M] = "
+        "act(X Wg^T) * (X Wu^T) from one staged X, act = silu or (gelu) "
+        "gelu_tanh as swiglu_mul; shapes as mtile_gemm_mxfp4",
+        py::arg("ACT"), py::arg("Wgq"), py::arg("Wgs"), py::arg("Wuq"),
+        py::arg("Wus"), py::arg("X"), py::arg("gelu"));
   m.def("route_env", &route_env,
         "device-side envelope routing (slot from header, dummy on stop)",
         py::arg("hdr"), py::arg("slot_out"), py::arg("pos_table"),

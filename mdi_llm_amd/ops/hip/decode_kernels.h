@@ -241,6 +241,17 @@ int launch_mtile_gemm(void* Y, const void* W, const void* X,
                       const void* bias, const void* res, int Bsz, int M,
                       int K, hipStream_t stream);
 
+// grouped M-tile MFMA GEMM on mxfp4 weights (layout of launch_gemv_mxfp4):
+// Y[B,M] = X[B,K] @ dequant(Wa)^T (+bias, +res), 1 <= B <= 128; with Wb/Sb
+// the fused form Y = act(X Wa^T) * (X Wb^T) (gelu_gate selects gelu_tanh).
+// K % 8 == 0, 32 <= K <= MTILE_MXFP4_MAX_K (a block keeps its rows' whole
+// scale rows in LDS), M % 16 == 0.  Returns -1 when the shape has no launch.
+#define MTILE_MXFP4_MAX_K 32768
+int launch_mtile_mxfp4(void* Y, const void* Wa, const void* Sa,
+                       const void* Wb, const void* Sb, const void* X,
+                       const void* bias, const void* res, int Bsz, int M,
+                       int K, int gelu_gate, hipStream_t stream);
+
 // envelope routing for the pipelined secondary serve: slot_out <-
 // hdr[0] (data) or dummy_slot (stop/flush, with pos reset)
 void launch_route_env(const int* hdr, int* slot_out, int* pos_table,

@@ -1356,6 +1356,306 @@ DEVINL float dot32_mxfp4(const i32x4_t wq, const x32w& x, float scale) {
 }
 
 // ---------------------------------------------------------------------------
+// Grouped-decode M-tile MFMA GEMM on MXFP4 weights:
+//   Y[B, M] = X[B, K] @ dequant(Wq)^T (+ bias) (+ res)             (!SWIGLU)
+//   ACT[B, M] = act(X @ Wg^T) * (X @ Wu^T), act = silu or gelu_tanh  (SWIGLU)
+// 1 <= B <= RB in {16, 32, 64, 128}; K % 8 == 0, K >= 32; M % 16 == 0.
+// Reads the packed bytes and the walk-order scale rows of quantize_mxfp4 as
+// they are (see above).  The skeleton is mtile_gemm_kernel's: X staged per
+// K chunk in LDS (bulk-coalesced, swizzled, prefetched through registers
+// into the other buffer), W streamed non-temporally through a two-slot ring
+// with compile-time slots, the 4 waves split each chunk, partials reduced
+// through LDS over the dead X buffers.
+//
+// Fragments.  Lane (r = lane&15, s = lane>>4) loads, per 128-k super-step t,
+// the 16 bytes of block 4t+s of row r: ONE load is one MX block and feeds
+// FOUR MFMAs per column tile.  Dword j of the block converts (four
+// v_cvt_scalef32_pk_bf16_fp4 with the block's 2^e, exact) into the bf16x8 A
+// fragment of MFMA j, which therefore contracts k = 128t + 32s + 8j + (0..7);
+// the matching X fragment of column b is one 16 B LDS read at that k.
+//
+// Scales: the scale rows of the block's row tiles are copied into LDS once
+// (coalesced dwords; rows padded by 16 B so that the 64 byte reads of a
+// super-step spread over the banks, unpadded where the pad would not fit)
+// and read from there per super-step.  Holding a whole scale row per output
+// row in LDS is what limits K: K <= MTILE_MXFP4_MAX_K = 32768 (1 KB of
+// scales per row, 32 rows beside 128 KB of X at RB >= 64).
+//
+// Geometry per RB (CB columns per pass, KC, row tiles per wave):
+//   16: 16, 1024, 1    32: 32, 512, 1    64: 64, 512, 2 (SWIGLU: 1)
+//   128: two passes of 64 columns over each chunk, 512, 2 (SWIGLU: 1)
+// A wave needs 128 k per super-step, so four waves need KC >= 512; at 128
+// columns two such buffers would be 256 KB, hence the two passes: the LDS
+// buffers alternate between the column halves and the (4 VGPR) weight slot
+// is converted once per pass.  At RB >= 64 every X fragment read feeds two
+// MFMAs (two row tiles, or gate + up).  LDS is 64 KB (RB <= 32) or 128 KB
+// plus the scales; rows B..RB-1 and k >= K are staged as zeros, weight
+// blocks past ceil(K/32) and row tiles past M are not loaded.
+// ---------------------------------------------------------------------------
+template <int KC>
+DEVINL int x_swz16(int row, int k) {  // element index into a [rows][KC] tile
+  int byte = (row * KC + k) * 2;
+  byte ^= (row & 15) << 4;
+  return byte >> 1;
+}
+
+template <int RB, bool SWIGLU>
+struct MtileMx {
+  static constexpr int CP = RB == 128 ? 2 : 1;   // column passes per chunk
+  static constexpr int CB = RB / CP;             // columns per pass
+  static constexpr int KC = CB == 16 ? 1024 : 512;
+  static constexpr int SS = KC / 512;            // super-steps per wave, chunk
+  static constexpr int NR = (RB >= 64 && !SWIGLU) ? 2 : 1;  // row tiles
+  static constexpr int NA = SWIGLU ? 2 : NR;     // A tiles per wave
+  static constexpr int XBYTES = 2 * CB * KC * 2;
+  static constexpr int LDS_MAX = 160 * 1024;
+  // scale row stride in LDS: SB bytes + 16 of bank-spreading pad, which is
+  // dropped where the padded rows would not fit beside the X buffers
+  // (K > 24576 at NA = 2 and 128 KB of X).  Unpadded, every
+  // K <= MTILE_MXFP4_MAX_K fits: 128 KB + 2 * 16 * 1024 B = 160 KB.
+  static __host__ __device__ int scale_stride(int K) {
+    const int sb = mxfp4_scale_dwords(K) * 4;
+    return XBYTES + NA * 16 * (sb + 16) <= LDS_MAX ? sb + 16 : sb;
+  }
+  static int smem_bytes(int K) { return XBYTES + NA * 16 * scale_stride(K); }
+};
+
+// bf16x8 A fragment from one dword (8 e2m1) and the block's scale
+DEVINL bf16x8_t mxfp4x8_to_bf16(unsigned w, float scale) {
+  unsigned p[4];
+  p[0] = __builtin_bit_cast(
+      unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 0));
+  p[1] = __builtin_bit_cast(
+      unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 1));
+  p[2] = __builtin_bit_cast(
+      unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 2));
+  p[3] = __builtin_bit_cast(
+      unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 3));
+  return *reinterpret_cast<const bf16x8_t*>(p);
+}
+
+template <int RB, bool SWIGLU>
+__global__ __launch_bounds__(256) void mtile_mxfp4_kernel(
+    bf16* __restrict__ Y,                     // [B, M]
+    const unsigned char* __restrict__ Wa,     // packed W (SWIGLU: gate)
+    const unsigned* __restrict__ Sa,          // its scale rows, as dwords
+    const unsigned char* __restrict__ Wb,     // SWIGLU: packed up
+    const unsigned* __restrict__ Sb,
+    const bf16* __restrict__ X,               // [B, K]
+    const bf16* __restrict__ bias, const bf16* __restrict__ res,
+    int B, int M, int K, int gelu_gate) {
+  using G = MtileMx<RB, SWIGLU>;
+  constexpr int CP = G::CP, CB = G::CB, KC = G::KC, SS = G::SS;
+  constexpr int NR = G::NR, NA = G::NA;
+  constexpr int CBT = CB / 16;            // 16-wide column tiles per pass
+  constexpr int PRE = CB * KC / 8 / 256;  // staged 16 B loads per thread
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  bf16* xbuf0 = reinterpret_cast<bf16*>(smem);
+  bf16* xbuf1 = xbuf0 + CB * KC;
+  unsigned char* sc_lds = reinterpret_cast<unsigned char*>(smem) + G::XBYTES;
+  // [4 waves][NA][RB cols][16 rows] fp32 <= 64 KB, over the dead X buffers
+  float* c_red = reinterpret_cast<float*>(smem);
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int arow = lane & 15;
+  const int sub = lane >> 4;
+  const int row0 = (int)blockIdx.x * (16 * NR);
+  const int nb = (K + 31) >> 5;           // blocks per row
+  const int nch = (K + KC - 1) / KC;
+  const int sbw = mxfp4_scale_dwords(K);  // scale dwords per row
+  const int sbp = G::scale_stride(K);     // LDS row stride, bytes
+
+  // A tile a: matrix a&1 under SWIGLU (one row tile), else row tile a
+  const unsigned char* wrow[NA];
+  bool rok[NA];
+#pragma unroll
+  for (int a = 0; a < NA; ++a) {
+    const int m = row0 + (SWIGLU ? 0 : a * 16) + arow;
+    rok[a] = m < M;
+    wrow[a] = ((SWIGLU && a == 1) ? Wb : Wa) + (size_t)m * nb * 16;
+  }
+
+  // ---- scale rows -> LDS ------------------------------------------------
+  for (int i = tid; i < NA * 16 * sbw; i += 256) {
+    const int a = i / (16 * sbw);
+    const int j = i - a * 16 * sbw;
+    const int r = j / sbw;
+    const int d = j - r * sbw;
+    const int m = row0 + (SWIGLU ? 0 : a * 16) + r;
+    const unsigned* src = (SWIGLU && a == 1) ? Sb : Sa;
+    const unsigned v = m < M ? src[(size_t)m * sbw + d] : 0x7f7f7f7fu;
+    *reinterpret_cast<unsigned*>(sc_lds + (a * 16 + r) * sbp + d * 4) = v;
+  }
+
+  f32x4 acc[CP][NA][CBT];
+#pragma unroll
+  for (int p = 0; p < CP; ++p)
+#pragma unroll
+    for (int a = 0; a < NA; ++a)
+#pragma unroll
+      for (int t = 0; t < CBT; ++t) acc[p][a][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  // thread i of a stage covers (column i / (KC/8), k8 = i % (KC/8) * 8)
+  auto xload = [&](int ci, int p, bf16x8 (&pre)[PRE]) {
+#pragma unroll
+    for (int u = 0; u < PRE; ++u) {
+      const int i = tid + u * 256;
+      const int c = i / (KC / 8);
+      const int k = ci * KC + (i - c * (KC / 8)) * 8;
+      const int b = p * CB + c;
+      bf16x8 v;
+      *reinterpret_cast<int4*>(v.v) = make_int4(0, 0, 0, 0);
+      if (b < B && k < K) v = load8(X + (size_t)b * K + k);
+      pre[u] = v;
+    }
+  };
+  auto xstore = [&](bf16* buf, bf16x8 (&pre)[PRE]) {
+#pragma unroll
+    for (int u = 0; u < PRE; ++u) {
+      const int i = tid + u * 256;
+      const int c = i / (KC / 8);
+      const int k8 = (i - c * (KC / 8)) * 8;
+      *reinterpret_cast<int4*>(&buf[x_swz16<KC>(c, k8)]) =
+          *reinterpret_cast<int4*>(pre[u].v);
+    }
+  };
+  // block index of this lane in super-step ss of chunk ci
+  const int q0 = wave * (KC / 4);
+  auto blk_of = [&](int ci, int ss) {
+    return ((ci * KC + q0 + ss * 128) >> 5) + sub;
+  };
+  auto wload = [&](int ci, i32x4_t (&wq)[SS][NA]) {
+#pragma unroll
+    for (int ss = 0; ss < SS; ++ss) {
+      const int blk = blk_of(ci, ss);
+#pragma unroll
+      for (int a = 0; a < NA; ++a) {
+        const i32x4_t z = {0, 0, 0, 0};
+        wq[ss][a] = (blk < nb && rok[a])
+                        ? load16_nt_u8(wrow[a] + (size_t)blk * 16)
+                        : z;
+      }
+    }
+  };
+
+  // W ring first (the loads fly across the X staging), then X of step 0
+  i32x4_t wring[2][SS][NA];
+  wload(0, wring[0]);
+  if (1 < nch) wload(1, wring[1]);
+  {
+    bf16x8 pre[PRE];
+    xload(0, 0, pre);
+    xstore(xbuf0, pre);
+  }
+  __syncthreads();
+
+  // one (chunk, column pass): ring slot, accumulators and LDS buffers are
+  // compile-time per call site (a runtime-indexed ring spills to scratch)
+  auto step = [&](int ci, int p, i32x4_t (&wq)[SS][NA],
+                  f32x4 (&ac)[NA][CBT], bf16* cur, bf16* nxt) {
+    bf16x8 pre[PRE];
+    const bool last_pass = p == CP - 1;
+    const bool more = !last_pass || ci + 1 < nch;
+    if (more) xload(last_pass ? ci + 1 : ci, last_pass ? 0 : p + 1, pre);
+#pragma unroll
+    for (int ss = 0; ss < SS; ++ss) {
+      const int kl = q0 + ss * 128;       // wave-uniform
+      if (ci * KC + kl < K) {
+        const int blk = blk_of(ci, ss);
+        // blocks past the row hold zero weights and take 2^0, whatever the
+        // row's own scales are
+        const bool inrow = blk < nb;
+        const int sidx = inrow ? (((blk >> 8) * 64 + (blk & 63)) * 4 +
+                                  ((blk >> 6) & 3))
+                               : 0;
+        bf16x8_t af[NA][4];
+#pragma unroll
+        for (int a = 0; a < NA; ++a) {
+          const unsigned e8 =
+              inrow ? sc_lds[(a * 16 + arow) * sbp + sidx] : 127u;
+          // byte -> 2^(e8-127) as FmtMxfp4::accum does
+          const float scale = __uint_as_float(e8 << 23);
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            af[a][j] = mxfp4x8_to_bf16((unsigned)wq[ss][a][j], scale);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+#pragma unroll
+          for (int t = 0; t < CBT; ++t) {
+            const bf16x8_t xf = *reinterpret_cast<const bf16x8_t*>(
+                &cur[x_swz16<KC>(t * 16 + arow, kl + sub * 32 + j * 8)]);
+#pragma unroll
+            for (int a = 0; a < NA; ++a)
+              ac[a][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                  af[a][j], xf, ac[a][t], 0, 0, 0);
+          }
+        }
+      }
+    }
+    if (last_pass && ci + 2 < nch) wload(ci + 2, wq);
+    if (more) xstore(nxt, pre);
+    __syncthreads();
+  };
+  for (int ci = 0; ci < nch; ci += 2) {
+    if constexpr (CP == 1) {
+      step(ci, 0, wring[0], acc[0], xbuf0, xbuf1);
+      if (ci + 1 < nch) step(ci + 1, 0, wring[1], acc[0], xbuf1, xbuf0);
+    } else {
+      step(ci, 0, wring[0], acc[0], xbuf0, xbuf1);
+      step(ci, 1, wring[0], acc[CP - 1], xbuf1, xbuf0);
+      if (ci + 1 < nch) {
+        step(ci + 1, 0, wring[1], acc[0], xbuf0, xbuf1);
+        step(ci + 1, 1, wring[1], acc[CP - 1], xbuf1, xbuf0);
+      }
+    }
+  }
+
+  // ---- intra-block K reduce through LDS + epilogue ----------------------
+  // c_red[wave][a][col][16 rows], rows rotated by col (moe_group_gemm_kernel)
+  constexpr int CW = RB * 16;  // floats per (wave, a)
+#pragma unroll
+  for (int p = 0; p < CP; ++p)
+#pragma unroll
+    for (int a = 0; a < NA; ++a)
+#pragma unroll
+      for (int t = 0; t < CBT; ++t) {
+        const int c = p * CB + t * 16 + arow;
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          c_red[(wave * NA + a) * CW + c * 16 + ((sub * 4 + r + c) & 15)] =
+              acc[p][a][t][r];
+      }
+  __syncthreads();
+  auto red = [&](int a, int c, int r) {
+    const int idx = a * CW + c * 16 + ((r + c) & 15);
+    return c_red[idx] + c_red[NA * CW + idx] + c_red[2 * NA * CW + idx] +
+           c_red[3 * NA * CW + idx];
+  };
+  constexpr int ROWS = 16 * NR;  // output rows of the block
+  for (int i = tid; i < ROWS * RB; i += 256) {
+    const int b = i / ROWS;
+    const int rr = i - b * ROWS;
+    const int m = row0 + rr;
+    if (b >= B || m >= M) continue;  // padding columns are never written
+    const size_t o = (size_t)b * M + m;
+    if constexpr (SWIGLU) {
+      const float g = red(0, b, rr);
+      const float u = red(1, b, rr);
+      const float act = gelu_gate ? gelu_tanh(g) : g / (1.f + expf(-g));
+      Y[o] = f2b(act * u);
+    } else {
+      float v = red(rr >> 4, b, rr & 15);
+      if (bias != nullptr) v += b2f(bias[m]);
+      if (res != nullptr) v += b2f(res[o]);
+      Y[o] = f2b(v);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Weight formats of the staged GEMVs.  The two skeletons below are written
 // once; a format struct carries exactly what differs between bf16, fp8 and
 // int4 weights.  Offsets and strides are in the format's own units (elem_t):
@@ -3763,6 +4063,59 @@ int launch_mtile_gemm(void* Y, const void* W, const void* X,
   MT_CASE(64, 256)
   MT_CASE(128, 128)
 #undef MT_CASE
+  return -1;
+}
+
+// grouped M-tile GEMM on mxfp4 weights; Wb/Sb non-null selects the fused
+// gate/up form.  Returns -1 when the shape has no launch (the bindings
+// refuse it first): B outside 1..128, K % 8, K < 32, M % 16, or
+// K > MTILE_MXFP4_MAX_K (up to there the scale rows fit the CU's LDS beside
+// the X buffers at every RB, see MtileMx::scale_stride).
+template <int RB, bool SWIGLU>
+static int launch_mtile_mx(void* Y, const void* Wa, const void* Sa,
+                           const void* Wb, const void* Sb, const void* X,
+                           const void* bias, const void* res, int Bsz, int M,
+                           int K, int gelu_gate, hipStream_t stream) {
+  using G = MtileMx<RB, SWIGLU>;
+  const int smem = G::smem_bytes(K);
+  if (smem > G::LDS_MAX) return -1;  // not reached for K <= MAX_K
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute(
+        reinterpret_cast<const void*>(&mtile_mxfp4_kernel<RB, SWIGLU>),
+        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    attr_set = true;
+  }
+  const int rows = 16 * G::NR;
+  hipLaunchKernelGGL((mtile_mxfp4_kernel<RB, SWIGLU>),
+                     dim3((M + rows - 1) / rows), dim3(256), (size_t)smem,
+                     stream, (bf16*)Y, (const unsigned char*)Wa,
+                     (const unsigned*)Sa, (const unsigned char*)Wb,
+                     (const unsigned*)Sb, (const bf16*)X, (const bf16*)bias,
+                     (const bf16*)res, Bsz, M, K, gelu_gate);
+  return 0;
+}
+
+int launch_mtile_mxfp4(void* Y, const void* Wa, const void* Sa,
+                       const void* Wb, const void* Sb, const void* X,
+                       const void* bias, const void* res, int Bsz, int M,
+                       int K, int gelu_gate, hipStream_t stream) {
+  if (Bsz < 1 || Bsz > 128 || K % 8 != 0 || K < 32 ||
+      K > MTILE_MXFP4_MAX_K || M < 16 || M % 16 != 0)
+    return -1;
+#define MX_CASE(RB)                                                         \
+  if (Bsz <= RB)                                                            \
+    return Wb != nullptr                                                    \
+               ? launch_mtile_mx<RB, true>(Y, Wa, Sa, Wb, Sb, X, nullptr,   \
+                                           nullptr, Bsz, M, K, gelu_gate,   \
+                                           stream)                          \
+               : launch_mtile_mx<RB, false>(Y, Wa, Sa, nullptr, nullptr, X, \
+                                            bias, res, Bsz, M, K, 0, stream);
+  MX_CASE(16)
+  MX_CASE(32)
+  MX_CASE(64)
+  MX_CASE(128)
+#undef MX_CASE
   return -1;
 }
 

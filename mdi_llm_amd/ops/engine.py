@@ -397,23 +397,28 @@ class _BlockWeights:
             setattr(self, n + "4", packed)
             setattr(self, n[:-2] + "_q", qparams)
 
+    def quantize_mxfp4_experts(self) -> None:
+        """MoE: attach the packed mxfp4 copies + scale rows of the three
+        expert slabs, cached on the mlp module like the fp8 ones
+        (quantize_fp8_experts): the single-sample and the grouped engine
+        of one stage share one packed copy."""
+        mlp, key = self._mlp, self._slab_key
+        cached = getattr(mlp, "_hip_expert_slabs_mxfp4", None)
+        if key is None or cached is None or cached[0] != key:
+            q = tuple(t for w_ in (self.fc1_w, self.fc2_w, self.mlp_proj_w)
+                      for t in quantize_mxfp4_slab(w_))
+            cached = (key, q)
+            mlp._hip_expert_slabs_mxfp4 = cached
+        (self.fc1_wmx, self.fc1_smx, self.fc2_wmx, self.fc2_smx,
+         self.mlp_proj_wmx, self.mlp_proj_smx) = cached[1]
+
     def quantize_mxfp4(self, config) -> None:
         """Attach packed mxfp4 copies (<name>_wmx) + e8m0 block scales
-        (<name>_smx) for the decode GEMVs.  MoE: the three expert slabs,
-        cached on the mlp module like the fp8 ones (quantize_fp8_experts);
-        the router weight stays bf16."""
+        (<name>_smx) for the decode GEMVs.  MoE: the three expert slabs
+        (quantize_mxfp4_experts); the router weight stays bf16."""
         names = ["attn_w", "proj_w"]
         if config.mlp_class_name == "LLaMAMoE":
-            mlp, key = self._mlp, self._slab_key
-            cached = getattr(mlp, "_hip_expert_slabs_mxfp4", None)
-            if key is None or cached is None or cached[0] != key:
-                q = tuple(t for w_ in (self.fc1_w, self.fc2_w,
-                                       self.mlp_proj_w)
-                          for t in quantize_mxfp4_slab(w_))
-                cached = (key, q)
-                mlp._hip_expert_slabs_mxfp4 = cached
-            (self.fc1_wmx, self.fc1_smx, self.fc2_wmx, self.fc2_smx,
-             self.mlp_proj_wmx, self.mlp_proj_smx) = cached[1]
+            self.quantize_mxfp4_experts()
         elif config.mlp_class_name in ("LLaMAMLP", "GemmaMLP"):
             names += ["mlp_proj_w", "fc1_w", "fc2_w"]
         else:

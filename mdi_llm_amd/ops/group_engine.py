@@ -28,8 +28,15 @@ with 16 <= B <= 128 reads every dense weight as packed MXFP4 (4.25 bits per
 weight, the tensors of ``quantize_mxfp4``) through the hand-written fp4-fed
 M-tile MFMA GEMMs: ``mtile_gemm_mxfp4`` for qkv, proj (+residual), down
 (+residual) and the lm_head, ``mtile_swiglu_mxfp4`` for gate and up in one
-launch (``_run_blocks_mxfp4``, ``self.mxfp4``).  Smaller groups, MoE stages,
-the CPU and shapes the kernels refuse keep the bf16 path and warn.
+launch (``_run_blocks_mxfp4``, ``self.mxfp4``).  Smaller groups, the CPU and
+shapes the kernels refuse keep the bf16 path and warn.  A MoE stage takes
+mxfp4 in its expert GEMMs alone (``self.moe_mxfp4``, every group size
+1..128): ``moe_group_swiglu_mxfp4`` / ``moe_group_down_mxfp4`` read the
+packed slabs the single-sample engine of the same stage uses (one copy,
+cached on the mlp module); router, qkv, proj and lm_head stay bf16.
+Measured on Mixtral-8x7B (``profiles/group_moe_mxfp4.md``): 1.61x / 1.79x /
+1.17x bf16 and 1.04x / 1.62x / 1.19x fp8 at group size 16 / 64 / 128, so the
+engine sets no upper bound on the path.
 Measured on Llama-3-8B (``profiles/group_mxfp4.md``): per shape the ops beat
 the bf16 library GEMMs at B=16 (all but down, 0.80x) and proj at B=32, and
 are SLOWER on every shape at B=64 and B=128; end to end the path is slower than
@@ -121,6 +128,17 @@ def _mxfp4_group_supported(config: ModelConfig, starter: bool,
             and all(m % 16 == 0 and m >= 16 for m in ms))
 
 
+def _moe_mxfp4_group_supported(config: ModelConfig, max_k: int) -> bool:
+    """The shape rule of moe_group_swiglu_mxfp4 / moe_group_down_mxfp4
+    (K % 32 == 0, 32 <= K <= max_k = ops.MTILE_MXFP4_MAX_K, M % 16 == 0):
+    n_embd and intermediate_size are each K of one expert GEMM and M of
+    the other."""
+    return (config.mlp_class_name == "LLaMAMoE"
+            and _moe_group_supported(config)
+            and all(32 <= d <= max_k
+                    for d in (config.n_embd, config.intermediate_size)))
+
+
 def group_engine_supported(config: ModelConfig) -> bool:
     if not (engine_supported(config)
             and config.norm_class_name == "RMSNorm"):
@@ -178,18 +196,29 @@ class GroupDecodeEngine:
                           "(int4 weights serve single-sample decode only)")
         # mxfp4 weights: the dense GEMMs of a group of 16..128 run on the
         # hand-written fp4-fed M-tile kernels (_run_blocks_mxfp4); smaller
-        # groups, MoE stages, the CPU and refused shapes keep bf16
+        # groups, the CPU and refused shapes keep bf16.  A MoE stage takes
+        # mxfp4 in its expert GEMMs alone, at every group size
+        # (moe_group_swiglu_mxfp4 / moe_group_down_mxfp4, self.moe_mxfp4).
+        want_mxfp4 = os.environ.get("MDI_WEIGHT_DTYPE", "bf16") == "mxfp4"
+        on_gpu = next(stage.parameters()).device.type == "cuda"
         self.mxfp4 = (
-            os.environ.get("MDI_WEIGHT_DTYPE", "bf16") == "mxfp4"
+            want_mxfp4
             and not self.moe
-            and next(stage.parameters()).device.type == "cuda"
+            and on_gpu
             and MXFP4_MIN_GROUP <= group_size <= MXFP4_MAX_GROUP
             and _mxfp4_group_supported(cfg, hasattr(stage, "lm_head"),
                                        self.ops.MTILE_MXFP4_MAX_K))
-        if os.environ.get("MDI_WEIGHT_DTYPE", "bf16") == "mxfp4":
+        self.moe_mxfp4 = (
+            want_mxfp4 and self.moe and on_gpu
+            and _moe_mxfp4_group_supported(cfg, self.ops.MTILE_MXFP4_MAX_K))
+        if want_mxfp4:
             import warnings
 
-            if self.mxfp4:
+            if self.moe_mxfp4:
+                warnings.warn("grouped MoE decode: MDI_WEIGHT_DTYPE=mxfp4 "
+                              "applies to the expert GEMMs; only the dense "
+                              "GEMMs (router, qkv, proj, lm_head) stay bf16")
+            elif self.mxfp4:
                 warnings.warn("grouped decode: MDI_WEIGHT_DTYPE=mxfp4 applies "
                               "to qkv, proj, the MLP and the lm_head "
                               "(mtile_gemm_mxfp4 / mtile_swiglu_mxfp4)")
@@ -222,6 +251,9 @@ class GroupDecodeEngine:
         if self.mxfp4:
             for w in self.blocks:
                 w.quantize_mxfp4(cfg)
+        if self.moe_mxfp4:
+            for w in self.blocks:
+                w.quantize_mxfp4_experts()
         if self.is_starter:
             self.wte = stage.transformer.wte.weight.detach().contiguous()
             self.lnf_w = stage.transformer.ln_f.weight.detach().contiguous()
@@ -481,6 +513,14 @@ class GroupDecodeEngine:
             ops.moe_group_down_fp8(self.D, w.mlp_proj_w8, w.mlp_proj_s,
                                    self.ACT, self.moe_count, self.moe_offset,
                                    self.B)
+        elif self.moe_mxfp4:
+            ops.moe_group_swiglu_mxfp4(self.ACT, w.fc1_wmx, w.fc1_smx,
+                                       w.fc2_wmx, w.fc2_smx, hn,
+                                       self.moe_count, self.moe_offset,
+                                       self.moe_perm, self.moe_escale, k)
+            ops.moe_group_down_mxfp4(self.D, w.mlp_proj_wmx, w.mlp_proj_smx,
+                                     self.ACT, self.moe_count,
+                                     self.moe_offset, self.B)
         else:
             ops.moe_group_swiglu(self.ACT, w.fc1_w, w.fc2_w, hn,
                                  self.moe_count, self.moe_offset,

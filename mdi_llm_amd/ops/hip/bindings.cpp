@@ -670,6 +670,98 @@ void moe_group_down_fp8(torch::Tensor D, torch::Tensor Wd,
                        "B <= 128, n_e <= 64, k <= 8");
 }
 
+// mxfp4 slab [n_e, M, ceil(K/32)*16] + scale rows [n_e, M, SB(K)], both
+// uint8 as quantize_mxfp4_slab returns them; K comes from the activations
+inline void check_mxfp4_slab(const char* op, const char* name,
+                             const torch::Tensor& W, const torch::Tensor& s,
+                             int64_t K, const torch::Device& dev) {
+  for (const torch::Tensor* t : {&W, &s})
+    TORCH_CHECK(t->is_cuda() && t->device() == dev &&
+                    t->scalar_type() == torch::kUInt8 &&
+                    t->is_contiguous() && t->dim() == 3,
+                op, ": ", name,
+                " and its scales must be contiguous 3-D uint8 on the "
+                "activations' device");
+  TORCH_CHECK(K % 32 == 0 && K >= 32 && K <= MTILE_MXFP4_MAX_K, op,
+              ": needs K % 32 == 0 and 32 <= K <= ", MTILE_MXFP4_MAX_K,
+              " (the scale rows of a block's rows stay in LDS), got ", K);
+  TORCH_CHECK(W.size(1) >= 16 && W.size(1) % 16 == 0, op,
+              ": needs M % 16 == 0, got ", W.size(1));
+  TORCH_CHECK(W.size(2) == K / 32 * 16, op, ": ", name,
+              " must be [n_e, M, K/32*16] for K = ", K);
+  TORCH_CHECK(s.size(0) == W.size(0) && s.size(1) == W.size(1) &&
+                  s.size(2) == mxfp4_scale_row_bytes((int)K),
+              op, ": ", name,
+              " scales must be [n_e, M, mxfp4_scale_row_bytes(K)]");
+  // 16 B weight loads and dword scale loads
+  TORCH_CHECK((uintptr_t)W.data_ptr() % 16 == 0 &&
+                  (uintptr_t)s.data_ptr() % 4 == 0,
+              op, ": ", name, " must be 16-byte, its scales dword aligned");
+}
+
+void moe_group_swiglu_mxfp4(torch::Tensor act, torch::Tensor Wgq,
+                            torch::Tensor Wgs, torch::Tensor Wuq,
+                            torch::Tensor Wus, torch::Tensor X,
+                            torch::Tensor count, torch::Tensor offset,
+                            torch::Tensor perm, torch::Tensor escale,
+                            int64_t k) {
+  const char* op = "moe_group_swiglu_mxfp4";
+  check_bf16(act, "act");
+  check_bf16(X, "X");
+  TORCH_CHECK(X.dim() == 2 && act.dim() == 2, op,
+              ": X [B,K], act [B*k,M]");
+  const int64_t B = X.size(0), K = X.size(1);
+  check_mxfp4_slab(op, "Wgq", Wgq, Wgs, K, X.device());
+  check_mxfp4_slab(op, "Wuq", Wuq, Wus, K, X.device());
+  const int64_t n_e = Wgq.size(0), M = Wgq.size(1);
+  TORCH_CHECK(Wuq.sizes() == Wgq.sizes(), op, ": Wuq shape");
+  TORCH_CHECK(B >= 1 && B <= 128, op, ": needs 1 <= B <= 128, got ", B);
+  TORCH_CHECK(act.device() == X.device() && act.size(0) == B * k &&
+                  act.size(1) == M,
+              op, ": size mismatch");
+  check_i32n(count, "count", n_e);
+  check_i32n(offset, "offset", n_e + 1);
+  check_i32n(perm, "perm", B * k);
+  check_f32(escale, "escale");
+  TORCH_CHECK(escale.numel() == B * k, "escale size");
+  const int rc = launch_moe_group_swiglu_mxfp4(
+      act.data_ptr(), Wgq.data_ptr(), Wgs.data_ptr(), Wuq.data_ptr(),
+      Wus.data_ptr(), X.data_ptr(), count.data_ptr<int>(),
+      offset.data_ptr<int>(), perm.data_ptr<int>(), escale.data_ptr<float>(),
+      (int)B, (int)n_e, (int)M, (int)K, (int)k, cur_stream());
+  TORCH_CHECK(rc == 0, op, ": needs K % 32 == 0, 32 <= K <= ",
+              MTILE_MXFP4_MAX_K, ", M % 16 == 0, B <= 128, n_e <= 64, "
+              "k <= 8");
+}
+
+void moe_group_down_mxfp4(torch::Tensor D, torch::Tensor Wdq,
+                          torch::Tensor Wds, torch::Tensor act,
+                          torch::Tensor count, torch::Tensor offset,
+                          int64_t n_tokens) {
+  const char* op = "moe_group_down_mxfp4";
+  check_f32(D, "D");
+  check_bf16(act, "act");
+  TORCH_CHECK(act.dim() == 2 && D.dim() == 2, op,
+              ": act [B*k,K], D [B*k,M]");
+  const int64_t R = act.size(0), K = act.size(1);
+  check_mxfp4_slab(op, "Wdq", Wdq, Wds, K, act.device());
+  const int64_t n_e = Wdq.size(0), M = Wdq.size(1);
+  TORCH_CHECK(n_tokens >= 1 && n_tokens <= 128 && R % n_tokens == 0, op,
+              ": rows must be n_tokens * k, 1 <= n_tokens <= 128");
+  TORCH_CHECK(D.device() == act.device() && D.size(0) == R &&
+                  D.size(1) == M,
+              op, ": size mismatch");
+  check_i32n(count, "count", n_e);
+  check_i32n(offset, "offset", n_e + 1);
+  const int rc = launch_moe_group_down_mxfp4(
+      D.data_ptr(), Wdq.data_ptr(), Wds.data_ptr(), act.data_ptr(),
+      count.data_ptr<int>(), offset.data_ptr<int>(), (int)n_tokens, (int)n_e,
+      (int)M, (int)K, (int)(R / n_tokens), cur_stream());
+  TORCH_CHECK(rc == 0, op, ": needs K % 32 == 0, 32 <= K <= ",
+              MTILE_MXFP4_MAX_K, ", M % 16 == 0, B <= 128, n_e <= 64, "
+              "k <= 8");
+}
+
 void moe_group_combine(torch::Tensor out, torch::Tensor res, torch::Tensor D,
                        torch::Tensor inv, int64_t k) {
   check_bf16(out, "out");
@@ -1270,6 +1362,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_group_down_fp8", &moe_group_down_fp8,
         "moe_group_down with an fp8(e4m3) slab + fp32 row scales [n_e, M]",
         py::arg("D"), py::arg("Wd"), py::arg("dscale"), py::arg("act"),
+        py::arg("count"), py::arg("offset"), py::arg("n_tokens"));
+  m.def("moe_group_swiglu_mxfp4", &moe_group_swiglu_mxfp4,
+        "moe_group_swiglu with mxfp4 slabs as quantize_mxfp4_slab returns "
+        "them: packed [n_e, M, K/32*16] + scale rows [n_e, M, "
+        "mxfp4_scale_row_bytes(K)]; K % 32 == 0, 32 <= K <= "
+        "MTILE_MXFP4_MAX_K, M % 16 == 0, 1 <= B <= 128",
+        py::arg("act"), py::arg("Wgq"), py::arg("Wgs"), py::arg("Wuq"),
+        py::arg("Wus"), py::arg("X"), py::arg("count"), py::arg("offset"),
+        py::arg("perm"), py::arg("escale"), py::arg("k"));
+  m.def("moe_group_down_mxfp4", &moe_group_down_mxfp4,
+        "moe_group_down with an mxfp4 slab + its scale rows (shapes as "
+        "moe_group_swiglu_mxfp4)",
+        py::arg("D"), py::arg("Wdq"), py::arg("Wds"), py::arg("act"),
         py::arg("count"), py::arg("offset"), py::arg("n_tokens"));
   m.def("moe_group_combine", &moe_group_combine,
         "out[b] = res[b] + sum over ranks of the token's expert rows",

@@ -123,6 +123,23 @@ int launch_moe_group_gemm_fp8(void* out, const void* Wa, const float* sa,
                               int n_e, int M, int K, int k_top, int swiglu,
                               hipStream_t stream);
 
+// the same on mxfp4 slabs: packed uint8 [n_e, M, ceil(K/32)*16] (Wg/Wu/Wd)
+// and walk-order scale rows uint8 [n_e, M, mxfp4_scale_row_bytes(K)]
+// (Sg/Su/Sd), as quantize_mxfp4 lays out each expert; activations and the
+// MFMA stay bf16 (moe_group_mxfp4_kernel).  K % 32 == 0, 32 <= K <=
+// MTILE_MXFP4_MAX_K (below), M % 16 == 0, 1 <= Bsz <= 128; -1 otherwise.
+int launch_moe_group_swiglu_mxfp4(void* act, const void* Wg, const void* Sg,
+                                  const void* Wu, const void* Su,
+                                  const void* X, const int* count,
+                                  const int* offset, const int* perm,
+                                  const float* escale, int Bsz, int n_e,
+                                  int M, int K, int k_top,
+                                  hipStream_t stream);
+int launch_moe_group_down_mxfp4(void* D, const void* Wd, const void* Sd,
+                                const void* act, const int* count,
+                                const int* offset, int Bsz, int n_e, int M,
+                                int K, int k_top, hipStream_t stream);
+
 // out[b] = res[b] + sum_rank D[inv[b*k + rank]] (fp32, rank order)
 void launch_moe_group_combine(void* out, const void* res, const float* D,
                               const int* inv, int Bsz, int E, int k,

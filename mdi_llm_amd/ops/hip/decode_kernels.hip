@@ -1656,6 +1656,306 @@ __global__ __launch_bounds__(256) void mtile_mxfp4_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// Grouped MoE expert GEMMs on MXFP4 slabs (quantize_mxfp4_slab: packed
+// [n_e, M, ceil(K/32)*16] and walk-order scale rows [n_e, M, SB]).  The
+// contract is moe_group_gemm_kernel's: grid (M/16, n_e), a block owns 16
+// output rows of ONE expert, returns before any weight load when the expert
+// got no token, reads its weight bytes from HBM exactly once, stages padding
+// rows of the last token tile as zeros and never writes them.  The feed is
+// mtile_mxfp4_kernel's: one 16 B load is one MX block and, converted with
+// the block's 2^e (exact), the bf16x8 A fragments of FOUR MFMAs per column
+// tile (eight under SWIGLU, where gate and up share the X fragment read).
+//
+// What is new is how X is staged.  Half a byte per weight lets a wave cover
+// 128 k per load, so four waves need KC >= 512, and LDS cannot hold two such
+// buffers for 128 token columns.  But an expert rarely has that many: at
+// B = 128, k = 2, 8 experts it gets about 32.  So the buffers hold CB <= 64
+// columns and the number of column passes over a chunk is a RUN-TIME
+// ceil(rows_used / CB): the common expert takes one pass, and only a crowded
+// one walks its register-resident weight slot again for a second pass (the
+// slot is converted once per pass; nothing is loaded twice).  The accumulators
+// of pass p are compile-time (acc[p], guarded by p < npass), the two LDS
+// buffers simply swap after every (chunk, pass).
+//
+// Geometry per MAXC = B rounded up to 16/32/64/128 (CB, KC, max passes):
+//   16: 16, 1024, 1    32: 32, 512, 1    64: 32, 512, 2    128: 64, 512, 2
+// (MAXC = 64 with one pass of 64 columns held one block per CU for a typical
+// 16 tokens per expert and lost to bf16, profiles/group_moe_mxfp4.md.)
+// LDS: the two X buffers (64 KB at CB <= 32, else 128 KB) plus the scale rows
+// of the block's 16 (SWIGLU: 2 x 16) weight rows, at most 160 KB at
+// K = MTILE_MXFP4_MAX_K.  That leaves no room for a row map, so the source
+// row of every staged column lives in ONE VGPR: the columns a wave stages are
+// wave-uniform (tid / (KC/8) + RS * u), lane l holds the source of column
+// wave*64/(KC/8) + RS*l, and v_readlane hands it to the staging loop as a
+// scalar.  The routing weights are fetched after the K loop, into the dead X
+// buffers beside the K-reduce scratch.
+// K % 32 == 0, 32 <= K <= MTILE_MXFP4_MAX_K, M % 16 == 0.  A token's
+// contraction order is (wave quarter of each KC chunk, chunks ascending):
+// a function of K and MAXC only.
+// ---------------------------------------------------------------------------
+template <int MAXC, bool SWIGLU>
+struct MoeMx {
+  static constexpr int CB = MAXC <= 32 ? MAXC : MAXC / 2;  // columns per pass
+  static constexpr int NP = MAXC / CB;              // column passes, at most
+  static constexpr int KC = CB == 16 ? 1024 : 512;
+  static constexpr int SS = KC / 512;  // super-steps per wave and chunk
+  static constexpr int NA = SWIGLU ? 2 : 1;
+  static constexpr int XBYTES = 2 * CB * KC * 2;
+  static constexpr int LDS_MAX = 160 * 1024;
+  // scale row stride in LDS, padded by 16 B while that fits (MtileMx)
+  static __host__ __device__ int scale_stride(int K) {
+    const int sb = mxfp4_scale_dwords(K) * 4;
+    return XBYTES + NA * 16 * (sb + 16) <= LDS_MAX ? sb + 16 : sb;
+  }
+  static int smem_bytes(int K) { return XBYTES + NA * 16 * scale_stride(K); }
+};
+
+template <int MAXC, bool SWIGLU>
+__global__ __launch_bounds__(256) void moe_group_mxfp4_kernel(
+    void* __restrict__ outp,                 // SWIGLU: bf16 [nrows, M]; else
+                                             // fp32 [nrows, M]
+    const unsigned char* __restrict__ Wa,    // packed gate (or down) slabs
+    const unsigned* __restrict__ Sa,         // their scale rows, as dwords
+    const unsigned char* __restrict__ Wb,    // SWIGLU: packed up slabs
+    const unsigned* __restrict__ Sb,
+    const bf16* __restrict__ X,              // SWIGLU: [B, K] tokens; else
+                                             // [nrows, K] permuted activations
+    const int* __restrict__ count, const int* __restrict__ offset,
+    const int* __restrict__ perm, const float* __restrict__ escale,
+    int M, int K, int k_top, int nrows) {
+  using G = MoeMx<MAXC, SWIGLU>;
+  constexpr int CB = G::CB, NP = G::NP, KC = G::KC, SS = G::SS, NA = G::NA;
+  constexpr int CBT = CB / 16;            // 16-wide column tiles per pass
+  constexpr int TPR = KC / 8;             // staging threads per column
+  constexpr int RS = 256 / TPR;           // columns per staging sweep
+  constexpr int PRE = CB / RS;            // staged 16 B loads per thread
+  const int e = blockIdx.y;
+  const int cnt = min(count[e], MAXC);
+  const int off = offset[e];
+  if (cnt <= 0 || off < 0 || off >= nrows) return;
+
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  bf16* xbuf0 = reinterpret_cast<bf16*>(smem);
+  bf16* xbuf1 = xbuf0 + CB * KC;
+  unsigned char* sc_lds = reinterpret_cast<unsigned char*>(smem) + G::XBYTES;
+  // after the K loop, over the dead X buffers:
+  // c_red[4 waves][NA][MAXC cols][16 rows] fp32 <= 64 KB, then MAXC weights
+  constexpr int CW = MAXC * 16;           // floats per (wave, a)
+  float* c_red = reinterpret_cast<float*>(smem);
+  float* sscale = c_red + 4 * NA * CW;
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int arow = lane & 15;
+  const int sub = lane >> 4;
+  const int row0 = (int)blockIdx.x * 16;
+  const int nb = K >> 5;                  // blocks per row (K % 32 == 0)
+  const int nch = (K + KC - 1) / KC;
+  const int sbw = mxfp4_scale_dwords(K);  // scale dwords per row
+  const int sbp = G::scale_stride(K);     // LDS row stride, bytes
+  const int nt = (cnt + 15) >> 4;         // token tiles in use
+  const int rows_used = nt * 16;
+  const int npass = NP == 1 ? 1 : (rows_used + CB - 1) / CB;
+
+  // permuted row -> the pair it holds (SWIGLU) / itself; -1: padding
+  auto pair_of = [&](int c) {
+    const int s = off + c;
+    if (c >= cnt || s >= nrows) return -1;
+    return SWIGLU ? min(max(perm[s], 0), nrows - 1) : s;
+  };
+  // lane l: source row of staged column wave*64/TPR + RS*l (see above)
+  const int col0 = (wave * 64) / TPR;
+  int mysrc = pair_of(col0 + RS * lane);
+  if (SWIGLU && mysrc >= 0) mysrc /= k_top;
+
+  const size_t wrow = (size_t)e * M + row0;
+  const unsigned char* wp[NA];
+#pragma unroll
+  for (int a = 0; a < NA; ++a)
+    wp[a] = (a == 1 ? Wb : Wa) + (wrow + arow) * (size_t)nb * 16;
+
+  // ---- scale rows -> LDS ------------------------------------------------
+  for (int i = tid; i < NA * 16 * sbw; i += 256) {
+    const int ar = i / sbw;               // a * 16 + row
+    const int d = i - ar * sbw;
+    const unsigned* src = ar >= 16 ? Sb : Sa;
+    *reinterpret_cast<unsigned*>(sc_lds + ar * sbp + d * 4) =
+        src[(wrow + (ar & 15)) * sbw + d];
+  }
+
+  f32x4 acc[NP][NA][CBT];
+#pragma unroll
+  for (int p = 0; p < NP; ++p)
+#pragma unroll
+    for (int a = 0; a < NA; ++a)
+#pragma unroll
+      for (int t = 0; t < CBT; ++t) acc[p][a][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  // thread i of a stage covers (column i / TPR + RS*u, k8 = i % TPR * 8)
+  const int xk = (tid - col0 * TPR) * 8;
+  auto xload = [&](int ci, int p, bf16x8 (&pre)[PRE]) {
+    const int k = ci * KC + xk;
+#pragma unroll
+    for (int u = 0; u < PRE; ++u) {
+      const int src = __builtin_amdgcn_readlane(mysrc, p * PRE + u);
+      bf16x8 v;
+      *reinterpret_cast<int4*>(v.v) = make_int4(0, 0, 0, 0);
+      if (src >= 0 && k < K) v = load8(X + (size_t)src * K + k);
+      pre[u] = v;
+    }
+  };
+  auto xstore = [&](bf16* buf, int p, bf16x8 (&pre)[PRE]) {
+#pragma unroll
+    for (int u = 0; u < PRE; ++u) {
+      const int c = col0 + RS * u;
+      if (p * CB + c < rows_used)
+        *reinterpret_cast<int4*>(&buf[x_swz16<KC>(c, xk)]) =
+            *reinterpret_cast<int4*>(pre[u].v);
+    }
+  };
+  // block index of this lane in super-step ss of chunk ci
+  const int q0 = wave * (KC / 4);
+  auto blk_of = [&](int ci, int ss) {
+    return ((ci * KC + q0 + ss * 128) >> 5) + sub;
+  };
+  auto wload = [&](int ci, i32x4_t (&wq)[SS][NA]) {
+#pragma unroll
+    for (int ss = 0; ss < SS; ++ss) {
+      const int blk = blk_of(ci, ss);
+#pragma unroll
+      for (int a = 0; a < NA; ++a) {
+        const i32x4_t z = {0, 0, 0, 0};
+        wq[ss][a] = blk < nb ? load16_nt_u8(wp[a] + (size_t)blk * 16) : z;
+      }
+    }
+  };
+
+  // W ring first (the loads fly across the X staging), then X of step 0
+  i32x4_t wring[2][SS][NA];
+  wload(0, wring[0]);
+  if (1 < nch) wload(1, wring[1]);
+  {
+    bf16x8 pre[PRE];
+    xload(0, 0, pre);
+    xstore(xbuf0, 0, pre);
+  }
+  __syncthreads();
+
+  // one (chunk, column pass): ring slot and accumulators are compile-time
+  // per call site (a runtime-indexed ring spills to scratch); the LDS
+  // buffers swap after every call
+  bf16* cur = xbuf0;
+  bf16* nxt = xbuf1;
+  auto step = [&](int ci, int p, i32x4_t (&wq)[SS][NA],
+                  f32x4 (&ac)[NA][CBT]) {
+    bf16x8 pre[PRE];
+    const bool last_pass = p == npass - 1;
+    const bool more = !last_pass || ci + 1 < nch;
+    const int nci = last_pass ? ci + 1 : ci;
+    const int np = last_pass ? 0 : p + 1;
+    if (more) xload(nci, np, pre);
+    const int ntp = nt - p * CBT;         // column tiles of this pass in use
+#pragma unroll
+    for (int ss = 0; ss < SS; ++ss) {
+      const int kl = q0 + ss * 128;       // wave-uniform
+      if (ci * KC + kl < K) {
+        const int blk = blk_of(ci, ss);
+        // blocks past the row hold zero weights and take 2^0
+        const bool inrow = blk < nb;
+        const int sidx = inrow ? (((blk >> 8) * 64 + (blk & 63)) * 4 +
+                                  ((blk >> 6) & 3))
+                               : 0;
+        bf16x8_t af[NA][4];
+#pragma unroll
+        for (int a = 0; a < NA; ++a) {
+          const unsigned e8 =
+              inrow ? sc_lds[(a * 16 + arow) * sbp + sidx] : 127u;
+          const float scale = __uint_as_float(e8 << 23);  // 2^(e8-127)
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            af[a][j] = mxfp4x8_to_bf16((unsigned)wq[ss][a][j], scale);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+#pragma unroll
+          for (int t = 0; t < CBT; ++t) {
+            if (t < ntp) {
+              const bf16x8_t xf = *reinterpret_cast<const bf16x8_t*>(
+                  &cur[x_swz16<KC>(t * 16 + arow, kl + sub * 32 + j * 8)]);
+#pragma unroll
+              for (int a = 0; a < NA; ++a)
+                ac[a][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                    af[a][j], xf, ac[a][t], 0, 0, 0);
+            }
+          }
+        }
+      }
+    }
+    if (last_pass && ci + 2 < nch) wload(ci + 2, wq);
+    if (more) xstore(nxt, np, pre);
+    __syncthreads();
+    bf16* t_ = cur;
+    cur = nxt;
+    nxt = t_;
+  };
+  for (int ci = 0; ci < nch; ci += 2) {
+#pragma unroll
+    for (int p = 0; p < NP; ++p)
+      if (p < npass) step(ci, p, wring[0], acc[p]);
+    if (ci + 1 < nch) {
+#pragma unroll
+      for (int p = 0; p < NP; ++p)
+        if (p < npass) step(ci + 1, p, wring[1], acc[p]);
+    }
+  }
+
+  // ---- intra-block K reduce through LDS + epilogue ----------------------
+  // c_red[wave][a][col][16 rows], rows rotated by col (moe_group_gemm_kernel)
+#pragma unroll
+  for (int p = 0; p < NP; ++p)
+#pragma unroll
+    for (int t = 0; t < CBT; ++t) {
+      if (p * CBT + t < nt) {
+        const int c = p * CB + t * 16 + arow;
+#pragma unroll
+        for (int a = 0; a < NA; ++a)
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            c_red[(wave * NA + a) * CW + c * 16 + ((sub * 4 + r + c) & 15)] =
+                acc[p][a][t][r];
+      }
+    }
+  if (SWIGLU && tid < MAXC) {
+    const int f = pair_of(tid);
+    sscale[tid] = f >= 0 ? escale[f] : 0.f;
+  }
+  __syncthreads();
+  auto red = [&](int a, int c, int r) {
+    const int idx = a * CW + c * 16 + ((r + c) & 15);
+    return c_red[idx] + c_red[NA * CW + idx] + c_red[2 * NA * CW + idx] +
+           c_red[3 * NA * CW + idx];
+  };
+  for (int i = tid; i < rows_used * 16; i += 256) {
+    const int c = i >> 4;
+    const int r = i & 15;
+    if (c >= cnt) continue;               // padding rows are never written
+    const int s = off + c;
+    if (s >= nrows) continue;
+    const size_t o = (size_t)s * M + row0 + r;
+    const float a = red(0, c, r);
+    if constexpr (SWIGLU) {
+      const float u = red(1, c, r);
+      const float act = a / (1.f + expf(-a));
+      // routing weight in fp32 before the bf16 rounding (as gemv_swiglu)
+      reinterpret_cast<bf16*>(outp)[o] = f2b(act * u * sscale[c]);
+    } else {
+      reinterpret_cast<float*>(outp)[o] = a;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Weight formats of the staged GEMVs.  The two skeletons below are written
 // once; a format struct carries exactly what differs between bf16, fp8 and
 // int4 weights.  Offsets and strides are in the format's own units (elem_t):
@@ -4457,6 +4757,85 @@ int launch_moe_group_gemm_fp8(void* out, const void* Wa, const float* sa,
   return moe_group_gemm_dispatch<true>(out, Wa, Wb, sa, sb, X, count, offset,
                                        perm, escale, Bsz, n_e, M, K, k_top,
                                        swiglu, stream);
+}
+
+// expert GEMMs on mxfp4 slabs; Wb/Sb non-null selects the SwiGLU form.
+// Returns -1 when the shape has no launch (the bindings refuse it first).
+template <int MAXC, bool SWIGLU>
+static int launch_moe_mx(void* out, const void* Wa, const void* Sa,
+                         const void* Wb, const void* Sb, const void* X,
+                         const int* count, const int* offset, const int* perm,
+                         const float* escale, int n_e, int M, int K,
+                         int k_top, int nrows, hipStream_t stream) {
+  using G = MoeMx<MAXC, SWIGLU>;
+  const int smem = G::smem_bytes(K);
+  if (smem > G::LDS_MAX) return -1;  // not reached for K <= MAX_K
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute(
+        reinterpret_cast<const void*>(&moe_group_mxfp4_kernel<MAXC, SWIGLU>),
+        hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_MAX);
+    attr_set = true;
+  }
+  hipLaunchKernelGGL((moe_group_mxfp4_kernel<MAXC, SWIGLU>),
+                     dim3(M / 16, n_e), dim3(256), (size_t)smem, stream, out,
+                     (const unsigned char*)Wa, (const unsigned*)Sa,
+                     (const unsigned char*)Wb, (const unsigned*)Sb,
+                     (const bf16*)X, count, offset, perm, escale, M, K, k_top,
+                     nrows);
+  return 0;
+}
+
+static int moe_group_mxfp4_dispatch(void* out, const void* Wa, const void* Sa,
+                                    const void* Wb, const void* Sb,
+                                    const void* X, const int* count,
+                                    const int* offset, const int* perm,
+                                    const float* escale, int Bsz, int n_e,
+                                    int M, int K, int k_top,
+                                    hipStream_t stream) {
+  if (M < 16 || M % 16 != 0 || K % 32 != 0 || K < 32 ||
+      K > MTILE_MXFP4_MAX_K || Bsz < 1 || Bsz > MOE_MAX_B || n_e < 1 ||
+      n_e > MOE_MAX_E || k_top < 1 || k_top > MOE_MAX_TOPK)
+    return -1;
+  const int nrows = Bsz * k_top;
+#define MOE_MX_CASE(MAXC)                                                    \
+  if (Bsz <= MAXC)                                                           \
+    return Wb != nullptr                                                     \
+               ? launch_moe_mx<MAXC, true>(out, Wa, Sa, Wb, Sb, X, count,    \
+                                           offset, perm, escale, n_e, M, K,  \
+                                           k_top, nrows, stream)             \
+               : launch_moe_mx<MAXC, false>(out, Wa, Sa, nullptr, nullptr,   \
+                                            X, count, offset, nullptr,       \
+                                            nullptr, n_e, M, K, k_top,       \
+                                            nrows, stream);
+  MOE_MX_CASE(16)
+  MOE_MX_CASE(32)
+  MOE_MX_CASE(64)
+  MOE_MX_CASE(128)
+#undef MOE_MX_CASE
+  return -1;
+}
+
+int launch_moe_group_swiglu_mxfp4(void* act, const void* Wg, const void* Sg,
+                                  const void* Wu, const void* Su,
+                                  const void* X, const int* count,
+                                  const int* offset, const int* perm,
+                                  const float* escale, int Bsz, int n_e,
+                                  int M, int K, int k_top,
+                                  hipStream_t stream) {
+  if (Wu == nullptr || Su == nullptr || perm == nullptr || escale == nullptr)
+    return -1;
+  return moe_group_mxfp4_dispatch(act, Wg, Sg, Wu, Su, X, count, offset, perm,
+                                  escale, Bsz, n_e, M, K, k_top, stream);
+}
+
+int launch_moe_group_down_mxfp4(void* D, const void* Wd, const void* Sd,
+                                const void* act, const int* count,
+                                const int* offset, int Bsz, int n_e, int M,
+                                int K, int k_top, hipStream_t stream) {
+  return moe_group_mxfp4_dispatch(D, Wd, Sd, nullptr, nullptr, act, count,
+                                  offset, nullptr, nullptr, Bsz, n_e, M, K,
+                                  k_top, stream);
 }
 
 void launch_moe_group_combine(void* out, const void* res, const float* D,

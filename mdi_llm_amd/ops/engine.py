@@ -23,7 +23,10 @@ shared norm, GptNeoxMLP, partial / no rotary, learned positions) at head
 size 64, 128 or 256, or 80 with q_per_kv 1.  That is also what lets the fp8
 KV cache (MDI_KV_DTYPE=fp8) turn on for a config.  MoE prompts
 (moe_prefill_supported): device-side routing for any length, then the
-grouped decode kernels or expert-major library GEMMs.
+grouped decode kernels or expert-major library GEMMs.  Many prompts prefill
+in one pass too (prefill_prompts / prefill_hidden_batch): their rows are
+packed, every token-wise stage runs once over the pack, and rope-append and
+attention are varlen kernels driven by one host-built table.
 """
 
 from __future__ import annotations
@@ -38,7 +41,9 @@ from ..models.model import KVCachePool
 from . import require_hip_ops
 
 __all__ = ["DecodeEngine", "engine_supported", "clamp_attn_chunks",
-           "moe_prefill_supported", "hip_prefill_supported"]
+           "moe_prefill_supported", "hip_prefill_supported",
+           "check_prefill_batch", "prefill_varlen_table",
+           "PREFILL_BATCH_MAX_TOKENS"]
 
 # attn_combine_kernel keeps chunk weights in 4 registers x 64 lanes
 ATTN_MAX_CHUNKS = 256
@@ -105,6 +110,64 @@ def hip_prefill_supported(config: ModelConfig) -> bool:
     return engine_supported(config) and (
         config.head_size in (64, 128, 256)
         or (config.head_size == 80 and config.q_per_kv == 1))
+
+
+# Batched prefill packs at most this many rows into one pass: the longest T
+# the prefill has been measured at.
+PREFILL_BATCH_MAX_TOKENS = 8192
+
+
+def check_prefill_batch(lens, slots, pos0s, max_seq: int, n_slots: int):
+    """The three lists of a varlen batch as int lists, or ValueError: equal
+    non-zero lengths, T >= 1, distinct slots in range, pos0 >= 0 and
+    pos0 + T <= max_seq."""
+    n = len(lens)
+    if n < 1 or len(slots) != n or len(pos0s) != n:
+        raise ValueError("lens, slots and pos0s must be non-empty lists of "
+                         f"one length ({n}, {len(slots)}, {len(pos0s)})")
+    lens, slots, pos0s = ([int(v) for v in l] for l in (lens, slots, pos0s))
+    if len(set(slots)) != n:
+        raise ValueError(f"duplicate slot in {slots}")
+    for i, (T, slot, pos0) in enumerate(zip(lens, slots, pos0s)):
+        if T < 1:
+            raise ValueError(f"sequence {i} has length {T}")
+        if not 0 <= slot < n_slots:
+            raise ValueError(f"slot {slot} out of range (n_slots={n_slots})")
+        if pos0 < 0 or pos0 + T > max_seq:
+            raise ValueError(f"sequence {i}: pos0 + T overflows the pool "
+                             f"(pos0={pos0} T={T} max_seq={max_seq})")
+    return lens, slots, pos0s
+
+
+def prefill_varlen_table(lens, slots, pos0s, qtpb: int, max_seq: int,
+                         n_slots: int, device) -> torch.Tensor:
+    """The int32 device table of one varlen prefill batch, built on the
+    CPU and copied once (no device sync); every layer reuses it:
+
+        cu[n+1] | slot[n] | pos0[n] | row_seq[T_total] | work[n_work][2]
+
+    work holds one (seq, q-tile group) entry per attention block, a group
+    being `qtpb` consecutive 16-row tiles of one sequence
+    (ops.prefill_varlen_qtpb(q_per_kv)), ordered by descending causal
+    length pos0 + last row: causal work grows with the position, so the
+    long tails start first and the short tiles fill the end of the launch.
+    Raises ValueError on lists no kernel may see."""
+    lens, slots, pos0s = check_prefill_batch(lens, slots, pos0s, max_seq,
+                                             n_slots)
+    cu = [0]
+    row_seq, work = [], []
+    for i, (T, pos0) in enumerate(zip(lens, pos0s)):
+        cu.append(cu[-1] + T)
+        row_seq += [i] * T
+        rows = 16 * qtpb
+        work += [(pos0 + min((q + 1) * rows, T) - 1, i, q)
+                 for q in range((T + rows - 1) // rows)]
+    work.sort(key=lambda e: -e[0])  # stable: ties keep (seq, tile) order
+    flat = cu + slots + pos0s + row_seq + [v for e in work for v in e[1:]]
+    device = torch.device(device)
+    tab = torch.tensor(flat, dtype=torch.int32,
+                       pin_memory=device.type == "cuda")
+    return tab.to(device, non_blocking=True)
 
 
 def quantize_fp8_rowwise(w: torch.Tensor):
@@ -936,12 +999,29 @@ class DecodeEngine:
                        pos0: int = 0) -> torch.Tensor:
         """Run the local blocks over a [T, n_embd] prompt chunk, filling the
         KV pool at positions pos0..pos0+T-1."""
+        ops = self.ops
+        pool = self.kv_pool
+        scale = 1.0 / (self.config.head_size ** 0.5)
+
+        def rope_attn(Y, qkv, li):
+            ops.rope_prefill_append(qkv, pool.k, pool.v, self.cos, self.sin,
+                                    pos0, slot, li, kscale=pool.kscale,
+                                    vscale=pool.vscale)
+            ops.prefill_attn(Y, qkv, pool.k, pool.v, pos0, slot, li, scale,
+                             kscale=pool.kscale, vscale=pool.vscale)
+
+        return self._prefill_blocks(x, rope_attn)
+
+    def _prefill_blocks(self, x: torch.Tensor, rope_attn) -> torch.Tensor:
+        """The local blocks over [T, n_embd] rows, one prompt or a pack of
+        them.  Every stage but two is token-wise; rope_attn(Y, qkv, layer)
+        does those two: rope q/k + append k/v, then causal attention into
+        Y."""
         import torch.nn.functional as F
 
         cfg = self.config
         ops = self.ops
         T = x.size(0)
-        scale = 1.0 / (cfg.head_size ** 0.5)
         Y = torch.empty(T, cfg.n_head * cfg.head_size, device=self.device,
                         dtype=torch.bfloat16)
         xn = torch.empty_like(x)
@@ -954,14 +1034,7 @@ class DecodeEngine:
         for li, w in enumerate(self.blocks):
             norm(xn, x, w.norm1_w, w.norm1_b)
             qkv = F.linear(xn, w.attn_w, w.attn_b)
-            ops.rope_prefill_append(qkv, self.kv_pool.k, self.kv_pool.v,
-                                    self.cos, self.sin, pos0, slot, li,
-                                    kscale=self.kv_pool.kscale,
-                                    vscale=self.kv_pool.vscale)
-            ops.prefill_attn(Y, qkv, self.kv_pool.k, self.kv_pool.v, pos0,
-                             slot, li, scale,
-                             kscale=self.kv_pool.kscale,
-                             vscale=self.kv_pool.vscale)
+            rope_attn(Y, qkv, li)
             # residual rides the GEMM epilogue (addmm beta=1) when there is
             # no bias; act(gate)*up is one fused launch instead of two
             if w.proj_b is None:
@@ -1094,6 +1167,96 @@ class DecodeEngine:
         if self.wpe is not None:
             x = x + self.wpe[pos0:pos0 + x.size(0)]
         return self.prefill_hidden(x, slot, pos0)
+
+    # ------------------------------------------------------------------
+    # batched prefill: many prompts packed into one [sum T_i, n_embd] pass
+    # ------------------------------------------------------------------
+    @torch.inference_mode()
+    def prefill_hidden_batch(self, x_packed: torch.Tensor, lens, slots,
+                             pos0s) -> list:
+        """prefill_hidden for n prompts at once: x_packed holds their rows
+        back to back, prompt i fills slots[i] from position pos0s[i].  Norms,
+        GEMMs and the MLP (MoE included) run once over the pack; rope-append and
+        attention are the varlen kernels (head size 64 / 128 / 256), or the
+        per-sequence ops over each prompt's row slice (head size 80, or
+        MDI_PREFILL_VARLEN_ATTN=0).  Packs hold at most
+        PREFILL_BATCH_MAX_TOKENS rows: the batch is split greedily, in
+        order, and a longer single prompt goes through prefill_hidden.
+        Returns the per-prompt [T_i, n_embd] views."""
+        cfg = self.config
+        ops = self.ops
+        pool = self.kv_pool
+        n_slots, max_seq = pool.k.size(0), pool.k.size(3)
+        qtpb = ops.prefill_varlen_qtpb(cfg.q_per_kv)
+        # every list is checked before the first pack launches anything
+        lens, slots, pos0s = check_prefill_batch(lens, slots, pos0s, max_seq,
+                                                 n_slots)
+        if x_packed.dim() != 2 or x_packed.size(0) != sum(lens):
+            raise ValueError(f"x_packed has {tuple(x_packed.shape)} rows, "
+                             f"the lengths sum to {sum(lens)}")
+        varlen = (cfg.head_size != 80 and os.environ.get(
+            "MDI_PREFILL_VARLEN_ATTN", "1") != "0")
+        scale = 1.0 / (cfg.head_size ** 0.5)
+        kv = dict(kscale=pool.kscale, vscale=pool.vscale)
+
+        outs, row, i = [], 0, 0
+        while i < len(lens):
+            j, rows = i + 1, lens[i]
+            while (j < len(lens)
+                   and rows + lens[j] <= PREFILL_BATCH_MAX_TOKENS):
+                rows += lens[j]
+                j += 1
+            x = x_packed[row:row + rows]
+            pl, ps, pp = lens[i:j], slots[i:j], pos0s[i:j]
+            if j == i + 1:
+                outs.append(self.prefill_hidden(x, ps[0], pp[0]))
+            else:
+                if varlen:
+                    tab = prefill_varlen_table(pl, ps, pp, qtpb, max_seq,
+                                               n_slots, self.device)
+
+                    def rope_attn(Y, qkv, li):
+                        ops.rope_prefill_append_varlen(
+                            qkv, pool.k, pool.v, self.cos, self.sin, tab,
+                            pl, ps, pp, li, **kv)
+                        ops.prefill_attn_varlen(Y, qkv, pool.k, pool.v, tab,
+                                                pl, ps, pp, li, scale, **kv)
+                else:
+                    def rope_attn(Y, qkv, li):
+                        r0 = 0
+                        for T, s, p in zip(pl, ps, pp):
+                            q = qkv[r0:r0 + T]
+                            ops.rope_prefill_append(q, pool.k, pool.v,
+                                                    self.cos, self.sin, p,
+                                                    s, li, **kv)
+                            ops.prefill_attn(Y[r0:r0 + T], q, pool.k,
+                                             pool.v, p, s, li, scale, **kv)
+                            r0 += T
+                outs += list(self._prefill_blocks(x, rope_attn).split(pl))
+            row += rows
+            i = j
+        return outs
+
+    @torch.inference_mode()
+    def prefill_prompts(self, tokens_list, slots, pos0s=None) -> list:
+        """Starter: embed every prompt, then prefill_hidden_batch."""
+        import torch.nn.functional as F
+
+        lens = [int(t.numel()) for t in tokens_list]
+        pos0s = [0] * len(lens) if pos0s is None else pos0s
+        pool = self.kv_pool
+        lens, slots, pos0s = check_prefill_batch(
+            lens, slots, pos0s, pool.k.size(3), pool.k.size(0))
+        toks = torch.cat([t.long().view(-1) for t in tokens_list])
+        x = F.embedding(toks, self.wte)
+        if self.config.scale_embeddings:
+            x = x * (self.config.n_embd ** 0.5)
+        if self.wpe is not None:
+            # learned positions, gathered by each row's own position
+            pos = torch.cat([torch.arange(p, p + T)
+                             for p, T in zip(pos0s, lens)])
+            x = x + self.wpe[pos.to(self.device)]
+        return self.prefill_hidden_batch(x, lens, slots, pos0s)
 
     # ------------------------------------------------------------------
     # fully-fused per-token step graphs (bench hot path)

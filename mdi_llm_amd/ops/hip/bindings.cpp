@@ -105,14 +105,15 @@ inline int64_t check_fp8_stack(const c10::optional<torch::Tensor>& eidx,
 struct PrefillGeom {
   int n_layers, n_kv, max_seq, hs, qpk, T;
   bool kv8;
+  int n_slots;
 };
 
-inline PrefillGeom check_prefill(const char* op, const torch::Tensor& qkv,
-                                 const torch::Tensor& kpool,
-                                 const torch::Tensor& vpool,
-                                 const c10::optional<torch::Tensor>& kscale,
-                                 const c10::optional<torch::Tensor>& vscale,
-                                 int64_t pos0, int64_t slot, int64_t layer) {
+// the part that does not know what a sequence is: dtypes, pool and qkv
+// shapes, the layer (T is the row count of qkv, one prompt or a pack)
+inline PrefillGeom check_prefill_pools(
+    const char* op, const torch::Tensor& qkv, const torch::Tensor& kpool,
+    const torch::Tensor& vpool, const c10::optional<torch::Tensor>& kscale,
+    const c10::optional<torch::Tensor>& vscale, int64_t layer) {
   check_bf16(qkv, "qkv");
   TORCH_CHECK(kscale.has_value() == vscale.has_value(), op,
               ": kscale and vscale go together");
@@ -152,13 +153,68 @@ inline PrefillGeom check_prefill(const char* op, const torch::Tensor& qkv,
   const int64_t qpk = qkv.size(1) / (n_kv * hs) - 2;
   TORCH_CHECK(qpk >= 1 && qkv.size(1) == n_kv * (qpk + 2) * hs, op,
               ": qkv width must be n_kv * (qpk + 2) * head_size, qpk >= 1");
-  TORCH_CHECK(pos0 >= 0 && pos0 + T <= max_seq, op,
-              ": pos0 + T overflows the pool (pos0=", pos0, " T=", T,
-              " max_seq=", max_seq, ")");
-  TORCH_CHECK(slot >= 0 && slot < n_slots, op, ": slot out of range");
   TORCH_CHECK(layer >= 0 && layer < n_layers, op, ": layer out of range");
   return PrefillGeom{(int)n_layers, (int)n_kv, (int)max_seq, (int)hs,
-                     (int)qpk, (int)T, kv8};
+                     (int)qpk, (int)T, kv8, (int)n_slots};
+}
+
+inline PrefillGeom check_prefill(const char* op, const torch::Tensor& qkv,
+                                 const torch::Tensor& kpool,
+                                 const torch::Tensor& vpool,
+                                 const c10::optional<torch::Tensor>& kscale,
+                                 const c10::optional<torch::Tensor>& vscale,
+                                 int64_t pos0, int64_t slot, int64_t layer) {
+  const PrefillGeom g =
+      check_prefill_pools(op, qkv, kpool, vpool, kscale, vscale, layer);
+  TORCH_CHECK(pos0 >= 0 && pos0 + g.T <= g.max_seq, op,
+              ": pos0 + T overflows the pool (pos0=", pos0, " T=", g.T,
+              " max_seq=", g.max_seq, ")");
+  TORCH_CHECK(slot >= 0 && slot < g.n_slots, op, ": slot out of range");
+  return g;
+}
+
+// A varlen batch: the host lists are the authority, checked in full before
+// any launch; the device table must have the size those lists imply.
+struct VarlenGeom {
+  int n_seq, T_total, n_work;
+};
+
+inline VarlenGeom check_varlen(const char* op, const PrefillGeom& g,
+                               const torch::Device& dev,
+                               const torch::Tensor& table,
+                               const std::vector<int64_t>& lens,
+                               const std::vector<int64_t>& slots,
+                               const std::vector<int64_t>& pos0s) {
+  const size_t n = lens.size();
+  TORCH_CHECK(n >= 1 && slots.size() == n && pos0s.size() == n, op,
+              ": lens, slots and pos0s must be non-empty lists of one "
+              "length");
+  std::vector<char> used(g.n_slots, 0);
+  const int qtpb = prefill_varlen_qtpb(g.qpk);
+  int64_t T_total = 0, n_work = 0;
+  for (size_t i = 0; i < n; ++i) {
+    TORCH_CHECK(lens[i] >= 1, op, ": sequence ", i, " has length ", lens[i]);
+    TORCH_CHECK(pos0s[i] >= 0 && pos0s[i] + lens[i] <= g.max_seq, op,
+                ": pos0 + T overflows the pool at sequence ", i, " (pos0=",
+                pos0s[i], " T=", lens[i], " max_seq=", g.max_seq, ")");
+    TORCH_CHECK(slots[i] >= 0 && slots[i] < g.n_slots, op,
+                ": slot out of range at sequence ", i);
+    TORCH_CHECK(!used[slots[i]], op, ": slot ", slots[i], " appears twice");
+    used[slots[i]] = 1;
+    T_total += lens[i];
+    n_work += ((lens[i] + 15) / 16 + qtpb - 1) / qtpb;
+  }
+  TORCH_CHECK(T_total == g.T, op, ": the lengths sum to ", T_total,
+              ", qkv has ", g.T, " rows");
+  TORCH_CHECK(T_total <= 65535, op, ": more than 65535 packed rows");
+  check_i32(table, "table");
+  TORCH_CHECK(table.is_contiguous() && table.device() == dev, op,
+              ": table must be contiguous on qkv's device");
+  const int64_t want = 3 * (int64_t)n + 1 + T_total + 2 * n_work;
+  TORCH_CHECK(table.dim() == 1 && table.numel() == want, op,
+              ": the table has ", table.numel(), " entries, these lists need ",
+              want);
+  return VarlenGeom{(int)n, (int)T_total, (int)n_work};
 }
 
 void rmsnorm(torch::Tensor out, torch::Tensor x, torch::Tensor w,
@@ -1255,6 +1311,71 @@ void prefill_attn(torch::Tensor out, torch::Tensor qkv, torch::Tensor kpool,
   TORCH_CHECK(rc == 0, "prefill_attn: unsupported head_size ", g.hs);
 }
 
+void rope_prefill_append_varlen(torch::Tensor qkv, torch::Tensor kpool,
+                                torch::Tensor vpool, torch::Tensor cos_t,
+                                torch::Tensor sin_t, torch::Tensor table,
+                                std::vector<int64_t> lens,
+                                std::vector<int64_t> slots,
+                                std::vector<int64_t> pos0s, int64_t layer,
+                                c10::optional<torch::Tensor> kscale,
+                                c10::optional<torch::Tensor> vscale) {
+  const char* op = "rope_prefill_append_varlen";
+  const PrefillGeom g =
+      check_prefill_pools(op, qkv, kpool, vpool, kscale, vscale, layer);
+  const VarlenGeom v =
+      check_varlen(op, g, qkv.device(), table, lens, slots, pos0s);
+  check_f32(cos_t, "cos");
+  check_f32(sin_t, "sin");
+  TORCH_CHECK(cos_t.sizes() == sin_t.sizes(), op,
+              ": cos and sin differ in shape");
+  // a 1-D (or zero-width) table switches rope off
+  const int64_t rope_ne = cos_t.dim() > 1 ? cos_t.size(1) : 0;
+  if (rope_ne > 0) {
+    TORCH_CHECK(cos_t.dim() == 2, op, ": cos must be 2-D");
+    TORCH_CHECK(rope_ne % 2 == 0 && rope_ne <= g.hs, op,
+                ": rope_ne must be even and <= head_size");
+    for (size_t i = 0; i < lens.size(); ++i)
+      TORCH_CHECK(cos_t.size(0) >= pos0s[i] + lens[i], op,
+                  ": the rope table has ", cos_t.size(0),
+                  " rows, sequence ", i, " ends at ", pos0s[i] + lens[i]);
+  }
+  launch_rope_prefill_append_varlen(
+      qkv.data_ptr(), kpool.data_ptr(), vpool.data_ptr(),
+      g.kv8 ? kscale->data_ptr<float>() : nullptr,
+      g.kv8 ? vscale->data_ptr<float>() : nullptr,
+      rope_ne ? cos_t.data_ptr<float>() : nullptr,
+      rope_ne ? sin_t.data_ptr<float>() : nullptr, table.data_ptr<int>(),
+      v.n_seq, v.T_total, g.n_slots, (int)layer, g.n_layers, g.n_kv,
+      g.max_seq, g.hs, (int)rope_ne, g.qpk, cur_stream());
+}
+
+void prefill_attn_varlen(torch::Tensor out, torch::Tensor qkv,
+                         torch::Tensor kpool, torch::Tensor vpool,
+                         torch::Tensor table, std::vector<int64_t> lens,
+                         std::vector<int64_t> slots,
+                         std::vector<int64_t> pos0s, int64_t layer,
+                         double scale, c10::optional<torch::Tensor> kscale,
+                         c10::optional<torch::Tensor> vscale) {
+  const char* op = "prefill_attn_varlen";
+  check_bf16(out, "out");
+  const PrefillGeom g =
+      check_prefill_pools(op, qkv, kpool, vpool, kscale, vscale, layer);
+  TORCH_CHECK(g.hs == 64 || g.hs == 128 || g.hs == 256, op,
+              ": unsupported head_size ", g.hs);
+  const VarlenGeom v =
+      check_varlen(op, g, qkv.device(), table, lens, slots, pos0s);
+  TORCH_CHECK(out.numel() == (int64_t)g.T * g.n_kv * g.qpk * g.hs &&
+                  out.device() == qkv.device(),
+              op, ": out size");
+  int rc = launch_prefill_attn_varlen(
+      out.data_ptr(), qkv.data_ptr(), kpool.data_ptr(), vpool.data_ptr(),
+      g.kv8 ? kscale->data_ptr<float>() : nullptr,
+      g.kv8 ? vscale->data_ptr<float>() : nullptr, table.data_ptr<int>(),
+      v.n_seq, v.T_total, v.n_work, g.n_slots, (int)layer, g.n_layers,
+      g.n_kv, g.max_seq, g.hs, g.qpk, (float)scale, cur_stream());
+  TORCH_CHECK(rc == 0, op, ": unsupported head_size ", g.hs);
+}
+
 void add(torch::Tensor out, torch::Tensor a, torch::Tensor b) {
   check_bf16(out, "out");
   check_bf16(a, "a");
@@ -1420,6 +1541,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("pos0"), py::arg("slot"), py::arg("layer"),
         py::arg("scale"), py::arg("kscale") = c10::nullopt,
         py::arg("vscale") = c10::nullopt);
+  m.def("rope_prefill_append_varlen", &rope_prefill_append_varlen,
+        "varlen prefill: rope q/k of a pack of prompts + append k/v to "
+        "each prompt's slot",
+        py::arg("qkv"), py::arg("kpool"), py::arg("vpool"), py::arg("cos"),
+        py::arg("sin"), py::arg("table"), py::arg("lens"), py::arg("slots"),
+        py::arg("pos0s"), py::arg("layer"),
+        py::arg("kscale") = c10::nullopt, py::arg("vscale") = c10::nullopt);
+  m.def("prefill_attn_varlen", &prefill_attn_varlen,
+        "varlen prefill: causal GQA flash attention over a pack of prompts",
+        py::arg("out"), py::arg("qkv"), py::arg("kpool"), py::arg("vpool"),
+        py::arg("table"), py::arg("lens"), py::arg("slots"),
+        py::arg("pos0s"), py::arg("layer"), py::arg("scale"),
+        py::arg("kscale") = c10::nullopt, py::arg("vscale") = c10::nullopt);
+  m.def("prefill_varlen_qtpb", &prefill_varlen_qtpb,
+        "q tiles a varlen attention block covers at this q_per_kv");
   m.def("attn_proj", &attn_proj,
         "fused GQA flash-decode attention + output projection (one "
         "launch; in-launch granule hand-off overlaps the proj weight "

@@ -298,3 +298,22 @@ int launch_prefill_attn(void* out, const void* qkv, const void* kpool,
                         int n_layers_pool, int n_kv_heads, int max_seq,
                         int head_size, int qpk, int T, float scale,
                         hipStream_t stream);
+
+// Varlen prefill over a pack of n_seq prompts, [T_total, qkv_dim].  tab is
+// the int32 device table cu[n_seq+1] | slot[n_seq] | pos0[n_seq] |
+// row_seq[T_total] | work[n_work][2] = (seq, q-tile group); a q-tile group
+// is prefill_varlen_qtpb(qpk) consecutive 16-row tiles of one sequence.
+int prefill_varlen_qtpb(int qpk);
+void launch_rope_prefill_append_varlen(
+    void* qkv, void* kpool, void* vpool, float* kscale, float* vscale,
+    const float* cos_t, const float* sin_t, const int* tab, int n_seq,
+    int T_total, int n_slots, int layer, int n_layers_pool, int n_kv_heads,
+    int max_seq, int head_size, int rope_ne, int qpk, hipStream_t stream);
+// head_size 64, 128, 256 at any qpk; else -1
+int launch_prefill_attn_varlen(void* out, const void* qkv, const void* kpool,
+                               const void* vpool, const float* kscale,
+                               const float* vscale, const int* tab,
+                               int n_seq, int T_total, int n_work,
+                               int n_slots, int layer, int n_layers_pool,
+                               int n_kv_heads, int max_seq, int head_size,
+                               int qpk, float scale, hipStream_t stream);

@@ -3913,6 +3913,336 @@ __global__ __launch_bounds__(256) void prefill_attn_mfma_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// Varlen prefill: many prompts packed into one [T_total, qkv_dim] activation.
+//
+// One int32 table describes the batch (built on the host, one H2D copy,
+// reused by every layer):
+//   cu[n+1]         row offsets of the sequences in the pack
+//   slot[n] pos0[n] KV slot and first position of each sequence
+//   row_seq[T_total] the sequence of every packed row
+//   work[n_work][2] attention work list, (seq, q-tile group) per entry,
+//                   ordered by descending causal length
+// The host checks the lists the table was built from before every launch;
+// the kernels check the entries they read against the pool geometry as
+// well and drop a block whose entry does not fit, so a table that does not
+// belong to the lists cannot address outside the pack or the pools.
+// ---------------------------------------------------------------------------
+struct VarlenSeq {
+  int row0, T, pos0, slot;
+  bool ok;
+};
+
+DEVINL VarlenSeq varlen_seq(const int* __restrict__ tab, int seq, int n_seq,
+                            int T_total, int n_slots, int max_seq) {
+  VarlenSeq s{0, 0, 0, 0, false};
+  if (seq < 0 || seq >= n_seq) return s;
+  s.row0 = tab[seq];
+  s.T = tab[seq + 1] - s.row0;
+  s.slot = tab[n_seq + 1 + seq];
+  s.pos0 = tab[2 * n_seq + 1 + seq];
+  s.ok = s.row0 >= 0 && s.T >= 1 && s.row0 + s.T <= T_total &&
+         s.slot >= 0 && s.slot < n_slots && s.pos0 >= 0 &&
+         s.pos0 + s.T <= max_seq;
+  return s;
+}
+
+// rope q/k of every packed row + append k/v to its sequence's slot: the
+// arithmetic of rope_prefill_append_kernel, the (slot, pos) of the row
+// looked up through row_seq.  grid (n_kv_heads, T_total).
+template <int KV8>
+__global__ void rope_prefill_append_varlen_kernel(
+    bf16* __restrict__ qkv, void* __restrict__ kpool_v,
+    void* __restrict__ vpool_v, float* __restrict__ kscale,
+    float* __restrict__ vscale, const float* __restrict__ cos_t,
+    const float* __restrict__ sin_t, const int* __restrict__ tab, int n_seq,
+    int T_total, int n_slots, int layer, int n_layers_pool, int n_kv_heads,
+    int max_seq, int head_size, int rope_ne, int qpk) {
+  using kvt = std::conditional_t<KV8 != 0, u8kv, bf16>;
+  kvt* kpool = reinterpret_cast<kvt*>(kpool_v);
+  kvt* vpool = reinterpret_cast<kvt*>(vpool_v);
+  __shared__ unsigned kvmax[2];
+  const int g = blockIdx.x;
+  const int row = blockIdx.y;
+  const VarlenSeq sq = varlen_seq(tab, tab[3 * n_seq + 1 + row], n_seq,
+                                  T_total, n_slots, max_seq);
+  const int t = row - sq.row0;
+  if (!sq.ok || t < 0 || t >= sq.T) return;  // block-uniform
+  const int pos = sq.pos0 + t;
+  const int slot = sq.slot;
+  const int tid = threadIdx.x;
+  const int half = rope_ne >> 1;
+  const int qkv_dim = n_kv_heads * (qpk + 2) * head_size;
+
+  bf16* base =
+      qkv + (size_t)row * qkv_dim + (size_t)g * (qpk + 2) * head_size;
+  for (int idx = tid; idx < (qpk + 1) * half; idx += blockDim.x) {
+    const int r = idx / half;
+    const int d = idx % half;
+    bf16* rw = base + (size_t)r * head_size;
+    const float x1 = b2f(rw[d]);
+    const float x2 = b2f(rw[d + half]);
+    const float c1 = cos_t[(size_t)pos * rope_ne + d];
+    const float s1 = sin_t[(size_t)pos * rope_ne + d];
+    const float c2 = cos_t[(size_t)pos * rope_ne + d + half];
+    const float s2 = sin_t[(size_t)pos * rope_ne + d + half];
+    rw[d] = f2b(x1 * c1 - x2 * s1);
+    rw[d + half] = f2b(x2 * c2 + x1 * s2);
+  }
+  if (KV8 && tid < 2) kvmax[tid] = 0;
+  __syncthreads();
+  const size_t head_row =
+      (((size_t)slot * n_layers_pool + layer) * n_kv_heads + g) *
+          (size_t)max_seq +
+      (size_t)pos;
+  const size_t cache_off = head_row * head_size;
+  const bf16* krow = base + (size_t)qpk * head_size;
+  const bf16* vrow = base + (size_t)(qpk + 1) * head_size;
+  if constexpr (KV8) {
+    float lk = 0.f, lv = 0.f;
+    for (int d = tid; d < head_size; d += blockDim.x) {
+      lk = fmaxf(lk, fabsf(b2f(krow[d])));
+      lv = fmaxf(lv, fabsf(b2f(vrow[d])));
+    }
+    lds_fmax_u(&kvmax[0], lk);
+    lds_fmax_u(&kvmax[1], lv);
+    __syncthreads();
+    const float ks = fmaxf(__uint_as_float(kvmax[0]), 1e-12f) / 448.f;
+    const float vs = fmaxf(__uint_as_float(kvmax[1]), 1e-12f) / 448.f;
+    for (int d = tid; d < head_size; d += blockDim.x) {
+      kpool[cache_off + d] = f32_to_fp8(b2f(krow[d]) / ks);
+      vpool[cache_off + d] = f32_to_fp8(b2f(vrow[d]) / vs);
+    }
+    if (tid == 0) {
+      kscale[head_row] = ks;
+      vscale[head_row] = vs;
+    }
+  } else {
+    for (int d = tid; d < head_size; d += blockDim.x) {
+      kpool[cache_off + d] = krow[d];
+      vpool[cache_off + d] = vrow[d];
+    }
+  }
+}
+
+// Causal flash attention over the pack.  The tile arithmetic is that of
+// prefill_attn_mfma_kernel (workgroup-shared K / V^T staging per chunk
+// across the GQA group, QK^T and P.V on MFMA 16x16x32, softmax state in
+// registers) and is kept as a copy of its own so that the single-prompt
+// kernel's register allocation cannot move.  The work split differs:
+//   * grid = n_work x n_kv_heads x n_hgrp, the work entry the SLOWEST index:
+//     the host orders the list by descending causal length, so every kv
+//     head's longest tiles are dispatched first and the short ones fill
+//     the tail of the launch;
+//   * a block's qtpb q tiles are consecutive tiles of ONE sequence (they
+//     share one staged K/V), rows past that sequence's T are staged as
+//     zeros and never written;
+//   * q / out rows are cu[seq] + t, pool rows are those of the sequence's
+//     own slot, the causal bound is pos0[seq] + t.
+template <int HS, int KV8, int PF_KCH>
+__global__ __launch_bounds__(256) void prefill_attn_varlen_kernel(
+    bf16* __restrict__ out,        // [T_total, n_head*HS]
+    const bf16* __restrict__ qkv,  // [T_total, qkv_dim], q already roped
+    const void* __restrict__ kpool_v, const void* __restrict__ vpool_v,
+    const float* __restrict__ kscale, const float* __restrict__ vscale,
+    const int* __restrict__ tab, int n_seq, int T_total, int n_work,
+    int n_slots, int layer, int n_layers_pool, int n_kv_heads, int max_seq,
+    int qpk, float scale, int hpb, int qtpb, int n_hgrp) {
+  using kvt = std::conditional_t<KV8 != 0, u8kv, bf16>;
+  const kvt* kpool = reinterpret_cast<const kvt*>(kpool_v);
+  const kvt* vpool = reinterpret_cast<const kvt*>(vpool_v);
+  __shared__ __attribute__((aligned(16))) bf16 k_lds[PF_KCH][HS + 16];
+  __shared__ __attribute__((aligned(16))) bf16 v_t[HS][PF_KCH + 24];
+  __shared__ __attribute__((aligned(16))) bf16 q_lds[ATTN_WAVES][16 * HS];
+  __shared__ __attribute__((aligned(16)))
+      bf16 p_t[ATTN_WAVES][16][PF_KCH + 24];
+
+  const int wave = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63;
+  int bid = blockIdx.x;
+  const int w = bid / (n_kv_heads * n_hgrp);  // work entry, heaviest first
+  bid -= w * (n_kv_heads * n_hgrp);
+  const int g = bid / n_hgrp;  // kv head
+  const int hgrp = bid % n_hgrp;
+  const int* work = tab + 3 * n_seq + 1 + T_total;
+  const VarlenSeq sq =
+      varlen_seq(tab, work[2 * w], n_seq, T_total, n_slots, max_seq);
+  const int qtg = work[2 * w + 1];
+  const int T = sq.T;
+  const int pos0 = sq.pos0;
+  const int n_qtiles = (T + 15) / 16;
+  // block-uniform, ahead of every barrier
+  if (!sq.ok || qtg < 0 || qtg * qtpb >= n_qtiles) return;
+
+  const int hj = hgrp * hpb + (wave % hpb);  // q row within the kv group
+  const int qtile = qtg * qtpb + (wave / hpb);
+  // wave/hpb >= qtpb when hpb does not divide 4 (hpb=3): idle that wave
+  const bool active =
+      (hj < qpk) && (qtile < n_qtiles) && (wave / hpb < qtpb);
+  const int h = g * qpk + hj;  // query head (output numbering)
+  const int q_base = qtile * 16;
+  const int qkv_dim = n_kv_heads * (qpk + 2) * HS;
+  const bf16* q_seq = qkv + (size_t)sq.row0 * qkv_dim;
+  bf16* out_seq = out + (size_t)sq.row0 * (n_kv_heads * qpk * HS);
+
+  const size_t scl_base =
+      (((size_t)sq.slot * n_layers_pool + layer) * n_kv_heads + g) *
+      (size_t)max_seq;
+  const size_t cache_base = scl_base * HS;
+
+  // stage this wave's 16 q rows (zeros when inactive or past the
+  // sequence's last row: the next packed row belongs to a neighbour)
+  for (int i = lane; i < 16 * (HS / 8); i += 64) {
+    const int r = i / (HS / 8);
+    const int d8 = (i % (HS / 8)) * 8;
+    int4 val = {0, 0, 0, 0};
+    const int t = q_base + r;
+    if (active && t < T)
+      val = *reinterpret_cast<const int4*>(
+          q_seq + (size_t)t * qkv_dim + ((size_t)g * (qpk + 2) + hj) * HS +
+          d8);
+    *reinterpret_cast<int4*>(&q_lds[wave][q_swz2<HS>(r, d8)]) = val;
+  }
+
+  // causal bounds: the block stages up to the last row any wave covers,
+  // a wave reads up to the last row of its own tile
+  const int qt_last = min(qtg * qtpb + qtpb, n_qtiles) * 16 - 1;
+  const int k_last_blk = pos0 + min(qt_last, T - 1) + 1;
+  const int k_last_w = active ? (pos0 + min(q_base + 15, T - 1) + 1) : 0;
+
+  const int arow = lane & 15;
+  const int sub = lane >> 4;
+  const int koff = sub * 8;
+  const int q_abs = pos0 + q_base + arow;
+  const int pkx = ((arow >> 3) & (PF_KCH / 8 - 1)) << 3;
+
+  float m_r = -1e30f, l_r = 0.f;
+  f32x4 o_pv[HS / 16];
+#pragma unroll
+  for (int s = 0; s < HS / 16; ++s) o_pv[s] = {0.f, 0.f, 0.f, 0.f};
+
+  const int n_ch = (k_last_blk + PF_KCH - 1) / PF_KCH;
+  for (int ch = 0; ch < n_ch; ++ch) {
+    const int key0 = ch * PF_KCH;
+    __syncthreads();  // previous chunk's readers done (q staging on ch 0)
+    // ---- cooperative K / V^T staging (fp8 dequantized once, here) ----
+    for (int i = threadIdx.x; i < PF_KCH * (HS / 8); i += 256) {
+      const int r = i / (HS / 8);
+      const int d8 = (i % (HS / 8)) * 8;
+      const int key = key0 + r;
+      bf16x8_t kk = {}, vv = {};
+      if (key < k_last_blk) {
+        const size_t off = cache_base + (size_t)key * HS + d8;
+        if constexpr (KV8) {
+          kk = fp8x8_to_bf16(kpool + off, kscale[scl_base + key]);
+          vv = fp8x8_to_bf16(vpool + off, vscale[scl_base + key]);
+        } else {
+          kk = *reinterpret_cast<const bf16x8_t*>(
+              reinterpret_cast<const bf16*>(kpool) + off);
+          vv = *reinterpret_cast<const bf16x8_t*>(
+              reinterpret_cast<const bf16*>(vpool) + off);
+        }
+      }
+      *reinterpret_cast<bf16x8_t*>(&k_lds[r][d8]) = kk;
+      // per-(row>>3) XOR on the key column, as in the single-prompt kernel
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int vrow = d8 + j;
+        const int kc = r ^ (((vrow >> 3) & (PF_KCH / 8 - 1)) << 3);
+        *reinterpret_cast<__bf16*>(&v_t[vrow][kc]) = vv[j];
+      }
+    }
+    __syncthreads();
+    if (!active || key0 >= k_last_w) continue;  // barriers are at loop top
+
+    // interior chunks skip the per-key mask compares (wave-uniform)
+    const bool full = (key0 + PF_KCH - 1) <= (pos0 + q_base);
+    float sc[PF_KCH / 16][4];
+#pragma unroll
+    for (int t4 = 0; t4 < PF_KCH / 16; ++t4) {
+      f32x4 a4 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int c = 0; c < HS / 32; ++c) {
+        const bf16x8_t af = *reinterpret_cast<const bf16x8_t*>(
+            &k_lds[t4 * 16 + arow][c * 32 + koff]);
+        const bf16x8_t bfr = *reinterpret_cast<const bf16x8_t*>(
+            &q_lds[wave][q_swz2<HS>(arow, c * 32 + koff)]);
+        a4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bfr, a4, 0, 0, 0);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int key = key0 + t4 * 16 + sub * 4 + r;
+        sc[t4][r] =
+            full ? a4[r] * scale
+                 : ((key <= q_abs && key < k_last_w) ? a4[r] * scale
+                                                     : -1e30f);
+      }
+    }
+    // ---- online softmax, state in registers (per q row = arow) ----
+    float tmax = -1e30f;
+#pragma unroll
+    for (int t4 = 0; t4 < PF_KCH / 16; ++t4)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) tmax = fmaxf(tmax, sc[t4][r]);
+    tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));
+    tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
+    const float m_new = fmaxf(m_r, tmax);
+    const float alpha = __expf(m_r - m_new);
+    m_r = m_new;
+    float psum = 0.f;
+#pragma unroll
+    for (int t4 = 0; t4 < PF_KCH / 16; ++t4)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float p = __expf(sc[t4][r] - m_new);  // masked: exactly 0
+        psum += p;
+        p_t[wave][arow][(t4 * 16 + sub * 4 + r) ^ pkx] = f2b(p);
+      }
+    psum += __shfl_xor(psum, 16, 64);
+    psum += __shfl_xor(psum, 32, 64);
+    l_r = l_r * alpha + psum;
+
+    // ---- P.V via MFMA (A = P rows from p_t, B = V^T slices) ----
+    float al[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) al[r] = __shfl(alpha, sub * 4 + r, 64);
+#pragma unroll
+    for (int s = 0; s < HS / 16; ++s)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) o_pv[s][r] *= al[r];
+#pragma unroll
+    for (int k2 = 0; k2 < PF_KCH / 32; ++k2) {
+      const bf16x8_t ap = *reinterpret_cast<const bf16x8_t*>(
+          &p_t[wave][arow][(k2 * 32 + koff) ^ pkx]);
+#pragma unroll
+      for (int s = 0; s < HS / 16; ++s) {
+        const int vrow = s * 16 + arow;
+        const int kc0 = (k2 * 32 + koff) ^
+                        (((vrow >> 3) & (PF_KCH / 8 - 1)) << 3);
+        const bf16x8_t vb =
+            *reinterpret_cast<const bf16x8_t*>(&v_t[vrow][kc0]);
+        o_pv[s] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ap, vb, o_pv[s],
+                                                          0, 0, 0);
+      }
+    }
+  }
+
+  // ---- normalize + write (lane holds q rows sub*4+r, dim s*16+arow) ----
+  if (active) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int t_out = q_base + sub * 4 + r;
+      const float lq = __shfl(l_r, sub * 4 + r, 64);
+      if (t_out >= T) continue;
+      const float inv = 1.f / lq;
+      bf16* op = out_seq + (size_t)t_out * (n_kv_heads * qpk * HS) +
+                 (size_t)h * HS + arow;
+#pragma unroll
+      for (int s = 0; s < HS / 16; ++s) op[s * 16] = f2b(o_pv[s][r] * inv);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Residual add: out = a + b (bf16, fp32 math)
 // ---------------------------------------------------------------------------
 __global__ void add_kernel(bf16* __restrict__ out, const bf16* __restrict__ a,
@@ -5213,6 +5543,65 @@ int launch_prefill_attn(void* out, const void* qkv, const void* kpool,
   PF_CASE(128)
   PF_CASE(256)
 #undef PF_CASE
+  return -1;
+}
+
+void launch_rope_prefill_append_varlen(
+    void* qkv, void* kpool, void* vpool, float* kscale, float* vscale,
+    const float* cos_t, const float* sin_t, const int* tab, int n_seq,
+    int T_total, int n_slots, int layer, int n_layers_pool, int n_kv_heads,
+    int max_seq, int head_size, int rope_ne, int qpk, hipStream_t stream) {
+  if (kscale != nullptr)
+    hipLaunchKernelGGL((rope_prefill_append_varlen_kernel<1>),
+                       dim3(n_kv_heads, T_total), dim3(256), 0, stream,
+                       (bf16*)qkv, kpool, vpool, kscale, vscale, cos_t,
+                       sin_t, tab, n_seq, T_total, n_slots, layer,
+                       n_layers_pool, n_kv_heads, max_seq, head_size,
+                       rope_ne, qpk);
+  else
+    hipLaunchKernelGGL((rope_prefill_append_varlen_kernel<0>),
+                       dim3(n_kv_heads, T_total), dim3(256), 0, stream,
+                       (bf16*)qkv, kpool, vpool, kscale, vscale, cos_t,
+                       sin_t, tab, n_seq, T_total, n_slots, layer,
+                       n_layers_pool, n_kv_heads, max_seq, head_size,
+                       rope_ne, qpk);
+}
+
+int prefill_varlen_qtpb(int qpk) {
+  const int hpb = qpk >= 4 ? 4 : qpk;
+  return hpb == 1 ? 4 : (hpb == 2 ? 2 : 1);
+}
+
+int launch_prefill_attn_varlen(void* out, const void* qkv, const void* kpool,
+                               const void* vpool, const float* kscale,
+                               const float* vscale, const int* tab,
+                               int n_seq, int T_total, int n_work,
+                               int n_slots, int layer, int n_layers_pool,
+                               int n_kv_heads, int max_seq, int head_size,
+                               int qpk, float scale, hipStream_t stream) {
+  // the block shape of the single-prompt v2 kernel: hpb q heads of one kv
+  // head x qtpb q tiles fill the 4 waves
+  const int hpb = qpk >= 4 ? 4 : qpk;
+  const int qtpb = prefill_varlen_qtpb(qpk);
+  const int n_hgrp = (qpk + hpb - 1) / hpb;
+  const int blocks = n_work * n_kv_heads * n_hgrp;
+  const int kv8 = kscale != nullptr;
+#define PFV_LAUNCH(H, K8)                                                   \
+  hipLaunchKernelGGL((prefill_attn_varlen_kernel<H, K8, 64>), dim3(blocks), \
+                     dim3(256), 0, stream, (bf16*)out, (const bf16*)qkv,    \
+                     kpool, vpool, kscale, vscale, tab, n_seq, T_total,     \
+                     n_work, n_slots, layer, n_layers_pool, n_kv_heads,     \
+                     max_seq, qpk, scale, hpb, qtpb, n_hgrp)
+#define PFV_CASE(H)                                                         \
+  if (head_size == H) {                                                     \
+    if (kv8) PFV_LAUNCH(H, 1); else PFV_LAUNCH(H, 0);                       \
+    return 0;                                                               \
+  }
+  PFV_CASE(64)
+  PFV_CASE(128)
+  PFV_CASE(256)
+#undef PFV_CASE
+#undef PFV_LAUNCH
   return -1;
 }
 

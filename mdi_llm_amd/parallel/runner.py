@@ -40,6 +40,10 @@ class TorchRunner:
         self.pos[slot] = tokens.numel()
         return x[0]  # (T, n_embd)
 
+    def prefill_heads(self, prompts, slots) -> list:
+        """prefill_head for every (prompt, slot) pair."""
+        return [self.prefill_head(p, s) for p, s in zip(prompts, slots)]
+
     @torch.inference_mode()
     def prefill_mid(self, x: torch.Tensor, slot: int) -> torch.Tensor:
         out = self.stage(x.view(1, -1, self.config.n_embd), slot=slot,
@@ -101,6 +105,17 @@ class HipRunner(TorchRunner):
             out = super().prefill_head(tokens, slot)
         self.engine.set_slot_pos(slot, self.pos[slot])
         return out
+
+    @torch.inference_mode()
+    def prefill_heads(self, prompts, slots) -> list:
+        """All prompts in one packed pass of the engine (one per slot)."""
+        if not self.engine.supports_hip_prefill:
+            return super().prefill_heads(prompts, slots)
+        outs = self.engine.prefill_prompts(prompts, slots)
+        for p, s in zip(prompts, slots):
+            self.pos[s] = p.numel()
+            self.engine.set_slot_pos(s, self.pos[s])
+        return outs
 
     @torch.inference_mode()
     def prefill_mid(self, x: torch.Tensor, slot: int) -> torch.Tensor:

@@ -69,6 +69,22 @@ class PipelineRuntime:
         self.device = device or torch.device("cpu")
         if world > 1:
             assert comm is not None
+        # MDI_PREFILL_BATCH=1: the starter prefills all prompts of a
+        # generate() in one packed pass (runner.prefill_heads).  Opt-in:
+        # batched GEMMs may pick other library kernels than per-prompt ones
+        self.prefill_batch = os.environ.get("MDI_PREFILL_BATCH", "0") == "1"
+
+    def _prefill_iter(self, prompts):
+        """(s, x) of the starter prefill of prompt s into slot s: one
+        prompt at a time, or under MDI_PREFILL_BATCH=1 all of them in one
+        pass up front."""
+        if self.prefill_batch:
+            ptoks = [p.to(self.device) for p in prompts]
+            yield from enumerate(self.runner.prefill_heads(
+                ptoks, list(range(len(ptoks)))))
+            return
+        for s, prompt in enumerate(prompts):
+            yield s, self.runner.prefill_head(prompt.to(self.device), s)
 
     # ------------------------------------------------------------------
     # starter
@@ -122,9 +138,7 @@ class PipelineRuntime:
 
         t_start = time.perf_counter()
         # ---- prefill: seed every sample into the ring --------------------
-        for s, prompt in enumerate(prompts):
-            ptoks = prompt.to(self.device)
-            x = runner.prefill_head(ptoks, s)
+        for s, x in self._prefill_iter(prompts):
             if self.world > 1:
                 self.comm.send(s, x, stop=False)
             else:
@@ -240,8 +254,7 @@ class PipelineRuntime:
         res = GenerationResult()
         seqs = [list(map(int, p.tolist())) for p in prompts]
         t_start = time.perf_counter()
-        for s, prompt in enumerate(prompts):
-            x = runner.prefill_head(prompt.to(self.device), s)
+        for s, x in self._prefill_iter(prompts):
             eng.slot.fill_(s)
             eng.tail_sample_step(x.view(-1, x.size(-1))[-1], s)
 
